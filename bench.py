@@ -18,6 +18,8 @@ Run: ``python bench.py [--gpus N --steps K --warmup W]``; for N > 1 under
 (also with N = 1: torchrun env -> a real 1-rank RCCL group, the collective path runs).
 ``--profile`` re-runs the same command under ``rocprofv3 --kernel-trace`` (before any GPU call)
 and prints a per-kernel table (tools/kstats.py); ``--profile pmc`` adds one counter pass.
+``--dump-outputs DIR`` writes the last timed step's result as ``.npy`` files (to compare two builds
+output for output); ``--full`` is where secondary measurements with runs of their own belong.
 Rank 0 prints ONE JSON line. Weights: seeded random-init VGG16 (no network for ImageNet
 weights); data: synthetic uint8 images. ``--device cpu --tiny`` is a functional rehearsal of the
 same code path (gloo, scaled model) used by the CPU test-suite.
@@ -83,6 +85,13 @@ def parse(argv=None):
                     help="--emulate-rccl-world: all-gather receive bandwidth per GPU (GB/s, xGMI ring)")
     ap.add_argument("--profile", nargs="?", const="trace", default=None, choices=["trace", "pmc"],
                     help="re-run under rocprofv3 and print a per-kernel table (trace) [+ PMC pass]")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32): "
+                         "filters [B, K], mosaic [n, 2S, 2S, 3] of a seeded sample of n images, mosaic_index [n]")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement or check that needs runs of its own; a plain run "
+                         "only sets up, warms up, times the steps and prints the result line (today the benchmark "
+                         "has no such extra, so the flag changes nothing yet)")
     return ap.parse_args(argv)
 
 
@@ -415,10 +424,30 @@ def main(argv=None):
                         f"{args.rccl_gbs} GB/s)")
         line["emulated_gather_bytes_per_step"] = int(rccl_dst.numel())
         line["emulated_gather_ms_per_step"] = round(rccl_dst.numel() / (args.rccl_gbs * 1e6), 3)
+    if args.dump_outputs and info.is_main and args.steps > 0:
+        _dump_outputs(args.dump_outputs, res, args.seed)
     if info.is_main:
         print(json.dumps(line), flush=True)
     pdist.shutdown()
     return line
+
+
+DUMP_IMAGES = 16  # 16 fp32 224px mosaics = 38.5 MB: the whole dump stays under 64 MB
+
+
+def _dump_outputs(path, res, seed):
+    """The last timed step's result (rank 0's batch) as float32 ``.npy`` files: every image's
+    selected filters, and the mosaics of a seeded sample of images, with the sample's indices.
+    Same arguments -> same inputs and same sample."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    B = res.filters.shape[0]
+    g = torch.Generator().manual_seed(seed)
+    idx = torch.randperm(B, generator=g)[:DUMP_IMAGES].sort().values
+    arrays = {"filters": res.filters, "mosaic": res.mosaic[idx.to(res.mosaic.device)], "mosaic_index": idx}
+    for k, t in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), t.detach().cpu().to(torch.float32).numpy())
 
 
 def _breakdown(eng, images, xbuf, args, sync):

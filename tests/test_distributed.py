@@ -225,6 +225,35 @@ def test_bench_rehearsal_dp2():
             assert k in line
 
 
+def test_bench_dump_outputs_rehearsal(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the last timed step's filters and a seeded sample of its mosaics as
+    float32 .npy files; the same arguments give the same inputs, sample and (on the CPU engine,
+    which is deterministic) the same arrays; --full is accepted and --steps sets the timed steps."""
+    import numpy as np
+
+    import bench
+
+    for v in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "DV_FORCE_PG", "TORCHELASTIC_RUN_ID"):
+        monkeypatch.delenv(v, raising=False)
+    B = bench.DUMP_IMAGES + 3  # more images than the dump keeps: the sampling path
+    base = ["--device", "cpu", "--tiny", "--batch", str(B), "--steps", "2", "--warmup", "1"]
+    runs = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        line = bench.main(base + extra + ["--dump-outputs", str(tmp_path / name)])
+        assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["n_gpus"] == 1
+        runs.append({p.stem: np.load(p) for p in sorted((tmp_path / name).glob("*.npy"))})
+    a, b = runs
+    assert sorted(a) == ["filters", "mosaic", "mosaic_index"]
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a["filters"].shape == (B, 4) and a["mosaic"].shape == (bench.DUMP_IMAGES, 64, 64, 3)
+    idx = a["mosaic_index"]
+    assert idx.shape == (bench.DUMP_IMAGES,) and np.all(np.diff(idx) > 0) and 0 <= idx[0] and idx[-1] < B
+    assert a["mosaic"].min() >= 0 and a["mosaic"].max() <= 255 and a["mosaic"].std() > 0
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+
+
 def test_shard_sizes():
     from deconv_api_amd.parallel.dist import shard_counts, shard_sizes
 

@@ -47,10 +47,20 @@ def test_rccl_reform_aborts_and_rebuilds():
 
 
 @pytest.mark.gpu
-def test_bench_under_torchrun_uses_rccl():
-    out = _torchrun(["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "8"])
+def test_bench_under_torchrun_uses_rccl(tmp_path):
+    out = _torchrun(["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "8",
+                     "--dump-outputs", str(tmp_path)])
     assert out["process_group"] == "nccl" and out["n_gpus"] == 1 and out["config"]["parallelism"] == "dp1"
     assert out["value"] > 0 and out["p50_req_latency_ms"] >= out["p50_batch_latency_ms"] * 0.5
+    assert out["steps"] == 2 and out["ms_per_step"] > 0
+    # --dump-outputs: the last timed step's filters and mosaics (all 8 images: fewer than the sample) as float32
+    import numpy as np
+
+    dump = {p.stem: np.load(p) for p in tmp_path.glob("*.npy")}
+    assert sorted(dump) == ["filters", "mosaic", "mosaic_index"] and all(v.dtype == np.float32 for v in dump.values())
+    assert dump["filters"].shape == (8, 4) and dump["filters"].min() >= -1 and dump["filters"].max() < 512
+    assert dump["mosaic_index"].tolist() == list(range(8)) and dump["mosaic"].shape == (8, 448, 448, 3)
+    assert dump["mosaic"].min() >= 0 and dump["mosaic"].max() <= 255 and dump["mosaic"].std() > 0
     # the step's compute stream was probed onto a hardware queue apart from RCCL's (parallel/dist.py:
     # pick_compute_stream): the async all-gather of step i overlaps step i+1 instead of queueing behind it
     assert out["collective_overlaps_compute"] is True, out
