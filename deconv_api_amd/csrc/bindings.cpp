@@ -8,6 +8,7 @@
 #include "jpeg_enc.h"
 #include "kernels.h"
 
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -153,6 +154,7 @@ int64_t conv(Tensor x, Tensor w, c10::optional<Tensor> bias, Tensor out, c10::op
              int64_t relu_cols, c10::optional<Tensor> out2, int64_t split_col, c10::optional<Tensor> obits,
              c10::optional<Tensor> ebits) {
   TORCH_CHECK(g.size() == 23, "conv: geometry vector must have 23 entries");
+  dv::g_route = dv::ConvRoute{};  // route report of this call (conv_route()); the launchers fill it
   check_cuda(x, "x");
   check_cuda(w, "w");
   check_cuda(out, "out");
@@ -418,6 +420,7 @@ int64_t conv(Tensor x, Tensor w, c10::optional<Tensor> bias, Tensor out, c10::op
       check_rc(dv::unpool2x2_launch(a.x, a.code, reinterpret_cast<uint16_t*>(unpooled.data_ptr()), a.N, a.H, a.W,
                                     a.C, a.code_div, a.relu_in, cur_stream()),
                "unpool2x2");
+      dv::g_route.flags |= dv::CR_F_UNPOOL;
       a.x = reinterpret_cast<const uint16_t*>(unpooled.data_ptr());
       a.x_elems = unpooled.numel();
       a.x_ld = a.C;
@@ -431,6 +434,7 @@ int64_t conv(Tensor x, Tensor w, c10::optional<Tensor> bias, Tensor out, c10::op
       const std::vector<int64_t> sz{a.N, a.H, a.W, a.C};
       const std::vector<int64_t> st{(int64_t)a.H * a.W * a.x_ld, (int64_t)a.W * a.x_ld, (int64_t)a.x_ld, 1};
       relu_x = at::relu(x.as_strided(sz, st));
+      dv::g_route.flags |= dv::CR_F_RELU_COPY;
       a.x = reinterpret_cast<const uint16_t*>(relu_x.data_ptr());
       a.x_elems = relu_x.numel();
       if (mask.has_value()) {  // the mask is staged with x's offsets: same dense layout
@@ -471,6 +475,8 @@ int64_t conv(Tensor x, Tensor w, c10::optional<Tensor> bias, Tensor out, c10::op
       const int cfg = dv::conv_dma_group_cfg(a, (int)amode, (int)epi);
       if (cfg != 0) {  // recorded (no split-K: the group runs its problems side by side); launched by conv_group_end
         g_group.push_back(PendingConv{a, (int)amode, (int)epi, cfg});
+        dv::g_route.kind = dv::CR_GROUP;
+        dv::g_route.cfg = cfg;
         return 0;
       }
     }
@@ -516,6 +522,47 @@ int64_t conv(Tensor x, Tensor w, c10::optional<Tensor> bias, Tensor out, c10::op
   }
   finish_stats();
   return 0;
+}
+
+// The kernel the last conv / conv_stem_pool call on this thread launched, e.g. "dma 128x128 st2 ks1",
+// "kw3p 256x256 lds sk", "kw3 256x256 + dma 128x128 tail m_base=65536", "unpool2x2 > dma 64x64 st3 ks1",
+// "group cfg8" (recorded in an open conv group, launched by conv_group_end). "none": no launch recorded.
+std::string conv_route() {
+  const dv::ConvRoute r = dv::g_route;
+  static const char* const kEpi[] = {"", " reg", " lds", " unpool", " pool", " strips", " persist", " pool_t", " pool_lds"};
+  const char* epi = (r.epi >= 0 && r.epi <= 8) ? kEpi[r.epi] : "";
+  char b[160];
+  switch (r.kind) {
+    case dv::CR_IGEMM: std::snprintf(b, sizeof b, "igemm %dx%d", r.bm, r.bn); break;
+    case dv::CR_HALO_V1: std::snprintf(b, sizeof b, "halo_v1%s", epi); break;
+    case dv::CR_HALO_V2: std::snprintf(b, sizeof b, "halo_v2"); break;
+    case dv::CR_POOL_V3: std::snprintf(b, sizeof b, "pool_v3"); break;
+    case dv::CR_C8_STREAM: std::snprintf(b, sizeof b, "c8_stream"); break;
+    case dv::CR_HS16:
+    case dv::CR_HS32:
+      std::snprintf(b, sizeof b, "%s oc%d%s%s%s", r.kind == dv::CR_HS16 ? "hs16" : "hs32", r.bn, epi,
+                    (r.flags & dv::CR_F_OCSPLIT) ? " ocsplit" : "", r.cfg == 1 ? " stem" : "");
+      break;
+    case dv::CR_PW: std::snprintf(b, sizeof b, "pw %dx%d", r.bm, r.bn); break;
+    case dv::CR_DMA:
+      std::snprintf(b, sizeof b, "dma %dx%d st%d ks%d%s%s", r.bm, r.bn, r.stages, r.ksplit, epi,
+                    (r.flags & dv::CR_F_MASK) ? " mask" : "");
+      break;
+    case dv::CR_KW3:
+    case dv::CR_KW3P: {
+      int n = std::snprintf(b, sizeof b, "%s %dx%d%s%s", r.kind == dv::CR_KW3 ? "kw3" : "kw3p", r.bm, r.bn, epi,
+                            (r.flags & dv::CR_F_SK) ? " sk" : "");
+      if ((r.flags & dv::CR_F_TAIL) && n > 0 && n < (int)sizeof b)
+        std::snprintf(b + n, sizeof b - n, " + dma 128x128 tail m_base=%d", r.m_base);
+      break;
+    }
+    case dv::CR_GROUP: std::snprintf(b, sizeof b, "group cfg%d", r.cfg); break;
+    default: std::snprintf(b, sizeof b, "none"); break;
+  }
+  std::string out;
+  if (r.flags & dv::CR_F_UNPOOL) out += "unpool2x2 > ";
+  if (r.flags & dv::CR_F_RELU_COPY) out += "relu_copy > ";
+  return out + b;
 }
 
 // kind 0 max / 1 avg; dir 0 fwd (in=x, out=y) / 1 bwd (in=gy, out=gx); geom = N,H,W,C,OH,OW,k,s,pad.
@@ -1379,6 +1426,7 @@ bool conv_stem_pool(Tensor x, Tensor w1, c10::optional<Tensor> b1, Tensor w2, c1
   a.out_code = out_code.data_ptr<uint8_t>();
   a.x_elems = avail_bytes(x) / 2;
   a.out_elems = avail_bytes(out) / 2;
+  dv::g_route = dv::ConvRoute{};
   const int rc = dv::conv3x3_stem_pool_launch(a, cur_stream());
   if (rc == -4) return false;
   check_rc(rc, "conv_stem_pool");
@@ -1463,6 +1511,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("stats_div") = 1, py::arg("ucode") = py::none(), py::arg("ucode_div") = 1,
         py::arg("relu_cols") = 0, py::arg("out2") = py::none(), py::arg("split_col") = 0,
         py::arg("obits") = py::none(), py::arg("ebits") = py::none());
+  m.def("conv_route", &conv_route, "kernel the last conv call on this thread launched (route report)");
   m.def("conv_group_begin", &conv_group_begin, "start recording groupable small-problem convs (this thread)");
   m.def("conv_group_pause", [](bool p) { g_group_paused = p; }, "suspend / resume recording (dependent convs)");
   m.def("conv_group_end", &conv_group_end, "launch the recorded convs as grouped kernels; returns the launch count");

@@ -77,6 +77,17 @@ __device__ __forceinline__ int row_xor(int row) {
 
 }  // namespace
 
+// Which pooled-max epilogue a tile can take: shared by conv_dma_body / epilogue (the choice) and dma_cfg (the
+// route report of that choice), so the report cannot drift from the kernel. LDS ring of a tile in bytes; the
+// transposed 8-B stores need 64-row waves; the LDS-staged form also the [BM/4][BN] values + codes in the ring.
+constexpr int dma_ring_bytes(int BM, int BN, int BK, int STAGES, bool MASK) {
+  return STAGES * ((MASK ? 2 : 1) * BM + BN) * BK * 2;
+}
+constexpr bool pool_t_fits(int FM) { return FM % 4 == 0; }
+constexpr bool pool_lds_fits(int FM, int BM, int BN, int ring_bytes) {
+  return pool_t_fits(FM) && BN % 16 == 0 && (BM / 4) * BN * 3 <= ring_bytes;
+}
+
 template <int DT, int FM, int FN, int EPI, bool accum>
 __device__ __forceinline__ void epilogue(const ConvArgs& a, const f32x4 (&acc)[FM][FN], int mw, int nw, int lane);
 template <int DT, int FM, int FN>
@@ -109,6 +120,7 @@ __device__ __forceinline__ void conv_dma_body(const ConvArgs& a, int tiles_n, in
   constexpr int B_BYTES = BN * ROWB;
   constexpr int M_BYTES = MASK ? A_BYTES : 0;
   constexpr int STAGE = A_BYTES + M_BYTES + B_BYTES;
+  static_assert(STAGES * STAGE == dma_ring_bytes(BM, BN, BK, STAGES, MASK), "ring size: one formula for kernel and launcher");
   constexpr int A_I = BM / RPI / NW;        // A DMA instructions per wave per K tile
   constexpr int B_GROUPS = BN / RPI;        // RPI-row groups of the B tile
   constexpr int B_FULL = B_GROUPS / NW, B_REM = B_GROUPS % NW;
@@ -391,7 +403,7 @@ __device__ __forceinline__ void conv_dma_body(const ConvArgs& a, int tiles_n, in
       return;
     }
   }
-  if constexpr (EPI == CONV_E_POOL && FM % 4 == 0 && BN % 16 == 0 && (BM / 4) * BN * 3 <= STAGES * STAGE) {
+  if constexpr (EPI == CONV_E_POOL && pool_lds_fits(FM, BM, BN, STAGES * STAGE)) {
     if (a.pool_t == 2) {
       __syncthreads();  // every wave is done reading the operand stages
       epilogue_pool_lds<DT, NW * 64, BM, BN, FM, FN>(a, acc, smem, m0, n0, wm, wn, lane, tid);
@@ -548,6 +560,9 @@ __device__ __forceinline__ void epilogue_pool_lds(const ConvArgs& a, const f32x4
                                                   int n0, int wm, int wn, int lane, int tid) {
   static_assert(FM % 4 == 0 && BN % 16 == 0, "pool LDS epilogue shape");
   constexpr int VROW = BN * 2, CROW = BN;  // bytes per pooled row: values / codes
+  // the code row's chunk swizzle stays inside the row (a 64-wide tile has 4 code chunks per pooled row, not 8:
+  // unmasked, its XOR term sent codes into other rows' chunks)
+  constexpr int CSWZ = CROW / 16 - 1;
   uint8_t* vs = smem;
   uint8_t* cs = smem + (BM / 4) * VROW;
   const int q = lane >> 4, cl = lane & 15, ce = cl & 1, cu = (cl >> 1) & 1, csub = cl & ~3, tsel = ce * 2 + cu;
@@ -593,7 +608,7 @@ __device__ __forceinline__ void epilogue_pool_lds(const ConvArgs& a, const f32x4
       const int cc = wn * FN * 16 + j * 16 + csub;                       // channel in the tile
       const int vch = (cc >> 3) ^ (((prl >> 2) & 3) << 1);
       *reinterpret_cast<uint2*>(vs + prl * VROW + (vch << 4) + (cc & 4) * 2) = make_uint2(w0, w1);
-      const int cch = (cc >> 4) ^ (((prl >> 2) & 3) | ((prl & 1) << 2));
+      const int cch = (cc >> 4) ^ ((((prl >> 2) & 3) | ((prl & 1) << 2)) & CSWZ);
       *reinterpret_cast<uint32_t*>(cs + prl * CROW + (cch << 4) + (cc & 12)) =
           (k0 & 0xFFu) | ((k0 >> 8) & 0xFF00u) | ((k1 & 0xFFu) << 16) | ((k1 >> 16) << 24);
     }
@@ -615,7 +630,7 @@ __device__ __forceinline__ void epilogue_pool_lds(const ConvArgs& a, const f32x4
 #pragma unroll
   for (int c = tid; c < (BM / 4) * CCPR; c += NT) {
     const int r = c / CCPR, pc = c % CCPR;
-    const int lc = pc ^ (((r >> 2) & 3) | ((r & 1) << 2));
+    const int lc = pc ^ ((((r >> 2) & 3) | ((r & 1) << 2)) & CSWZ);
     const int col = n0 + lc * 16;
     if (prow0 + r >= prows || col >= a.OC) continue;
     *reinterpret_cast<uint4*>(a.out_code + (long long)(prow0 + r) * a.OC + col) =
@@ -625,7 +640,7 @@ __device__ __forceinline__ void epilogue_pool_lds(const ConvArgs& a, const f32x4
 
 template <int DT, int FM, int FN, int EPI, bool accum>
 __device__ __forceinline__ void epilogue(const ConvArgs& a, const f32x4 (&acc)[FM][FN], int mw, int nw, int lane) {
-  if constexpr (EPI == CONV_E_POOL && FM % 4 == 0) {
+  if constexpr (EPI == CONV_E_POOL && pool_t_fits(FM)) {
     if (a.pool_t) {
       epilogue_pool_t<DT, FM, FN>(a, acc, mw, nw, lane);
       return;
@@ -1649,7 +1664,8 @@ static int num_cus() {
 }
 
 // DV_KW3: 0 disables the shared-kw-tap kernel (A/B), 2 forces it for every eligible launch regardless
-// of the grid size (tests: small shapes with many image borders per tile). Read per launch.
+// of the grid size and ahead of the small-problem tile choice (dma_bn; tests: small shapes with many
+// image borders per tile). Read per launch.
 static int kw3_mode() {
   const char* e = dv_ab_env("DV_KW3");
   return e ? std::atoi(e) : 1;
@@ -1727,6 +1743,7 @@ static int kw3_try(const ConvArgs& a, hipStream_t s, int tiles_m_limit = 0) {
       auto launch_p = [&](auto em) -> int {
         constexpr int U = decltype(em)::value;
         const unsigned g = (unsigned)(nwg < (long long)num_cus() ? nwg : (long long)num_cus());
+        route_set(CR_KW3P, BM, BN, 0, 0, U == 1 ? CR_E_UNPOOL : (U == 2 ? CR_E_LDS : CR_E_REG));
         if constexpr (DT == DT_BF16) {
           if (var == 10) {
             hipLaunchKernelGGL((conv_dma_kw3p_kernel<DT, BN, BM, U, 1>), dim3(g), dim3(512), 0, s, a, tiles_n, (int)nwg, kw3p_pre());
@@ -1757,6 +1774,7 @@ static int kw3_try(const ConvArgs& a, hipStream_t s, int tiles_m_limit = 0) {
         }
         if (tiles_m_limit == 0 && kw3_sk_ok(a, BM, BN)) {  // stream-K over the whole grid (no tail launch)
           const int G = num_cus();
+          g_route.flags |= CR_F_SK;
           if (hipMemsetAsync(a.skflag, 0, (size_t)G * sizeof(unsigned), s) != hipSuccess) return (int)hipGetLastError();
           hipLaunchKernelGGL((conv_dma_kw3p_kernel<DT, BN, BM, U, 0, true>), dim3(G), dim3(512), 0, s, a, tiles_n,
                              (int)nwg, kw3p_pre());
@@ -1784,6 +1802,7 @@ static int kw3_try(const ConvArgs& a, hipStream_t s, int tiles_m_limit = 0) {
           a.H < 4096 && 2LL * a.H * a.W + BM < (1LL << 19) && dv_ab_env("DV_NO_KW3P_UNPOOL") == nullptr)
         return launch_p(std::integral_constant<int, 1>{});
     }
+    route_set(CR_KW3, BM, BN, 0, 0, CR_E_NONE);
     if constexpr (DT == DT_BF16 && EPI == CONV_E_BF16) {
       if (var == 8 || var == 9) {
         if (var == 8)
@@ -1809,6 +1828,12 @@ static int dma_cfg(const ConvArgs& a, hipStream_t s) {
   if (nwg <= 0 || nwg > 0x7fffffffLL) return -2;
   const bool aligned = (a.C % BK) == 0;
   const dim3 grid((unsigned)nwg, (unsigned)(a.ws ? a.ksplit : 1));
+  int epi_kind = CR_E_NONE;
+  if constexpr (EPI == CONV_E_POOL) {  // the pooled-max epilogue conv_dma_body takes: the kernel's own conditions
+    constexpr bool lds_fits = pool_lds_fits(FM, BM, BN, dma_ring_bytes(BM, BN, BK, ST, MASK));
+    epi_kind = (lds_fits && a.pool_t == 2) ? CR_E_POOL_LDS : ((pool_t_fits(FM) && a.pool_t) ? CR_E_POOL_T : CR_E_POOL);
+  }
+  route_set(CR_DMA, BM, BN, ST, a.ws ? a.ksplit : 1, epi_kind, MASK ? CR_F_MASK : 0);
   if (aligned)
     hipLaunchKernelGGL((conv_dma_kernel<DT, WM, WN, FM, FN, BK, ST, AMODE, EPI, true, MASK, FP>), grid,
                        dim3(NT), 0, s, a, tiles_n);
@@ -1838,7 +1863,12 @@ static int kw3_split(const ConvArgs& a, hipStream_t s, long long cus) {
   if (rc != 0) return rc;  // -4 (unsupported) before anything launched, or a launch error
   ConvArgs t = a;
   t.m_base = (int)(main_m * 256);
-  return dma_cfg<DT, 4, 2, 2, 4, 64, 2, AMODE, EPI>(t, s);  // 128 x 128 tail
+  const ConvRoute main_route = g_route;  // the report keeps the main launch, plus the tail flag and its first row
+  const int trc = dma_cfg<DT, 4, 2, 2, 4, 64, 2, AMODE, EPI>(t, s);  // 128 x 128 tail
+  g_route = main_route;
+  g_route.flags |= CR_F_TAIL;
+  g_route.m_base = t.m_base;
+  return trc;
 }
 
 // Measured and removed (rounds 1-3, profiles/layers_r1_dmav{0,5,6}.txt, layers_r1_ks2_{off,on}.txt,
@@ -1906,6 +1936,15 @@ static int auto_cfg(const ConvArgs& a) {
 template <int DT, int AMODE, int EPI>
 static int dma_bn(const ConvArgs& a, hipStream_t s) {
   if (g_cfg > 0) return dma_forced<DT, AMODE, EPI>(a, s, g_cfg);
+  // DV_KW3=2 forces the shared-tap kernel ahead of the measured small-problem tiles below too (the tests'
+  // small shapes, K = 9 C < 1024 or few rows, would all take those). Read per launch and only under
+  // DV_ABLATIONS=1 (kw3_mode() is 1 otherwise: a serving process keeps its dispatch whatever its environment holds).
+  if (kw3_mode() == 2) {
+    const int rc = (a.OCpad % 256 == 0 && a.OC > 128) ? kw3_try<DT, AMODE, EPI>(a, s)
+                   : (a.OCpad % 128 == 0 && a.OC > 64) ? kw3_try<DT, AMODE, EPI, 128, 512>(a, s)
+                                                        : -4;
+    if (rc != -4) return rc;
+  }
   if (const int c = auto_cfg(a)) return dma_forced<DT, AMODE, EPI>(a, s, c);
   // (the 3-stage BK=64 ring wins slightly on 256x128; 2 stages elsewhere)
   const long long cus = num_cus();

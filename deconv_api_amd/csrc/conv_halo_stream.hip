@@ -894,7 +894,9 @@ int conv3x3_hs_launch(const ConvArgs& a, int epi, hipStream_t s, bool* lepi_used
     // both halves must be supported before either launches
     const int r1 = conv3x3_hs_launch(a1, epi, s);
     if (r1 < 0) return r1;
-    return conv3x3_hs_launch(a2, epi, s);
+    const int r2 = conv3x3_hs_launch(a2, epi, s);
+    g_route.flags |= CR_F_OCSPLIT;
+    return r2;
   }
   // 3x3 / stride 1, symmetric pad 0..2 (output = input + 2 pad - 2)
   const bool geom = a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad_h == a.pad_w && a.pad_h >= 0 && a.pad_h <= 2 &&
@@ -926,6 +928,7 @@ int conv3x3_hs_launch(const ConvArgs& a, int epi, hipStream_t s, bool* lepi_used
                       !(reinterpret_cast<uintptr_t>(a.out) & 15) &&
                       (!a.emask || (a.emask_ld % 8 == 0 && !(reinterpret_cast<uintptr_t>(a.emask) & 15)));
     if (lepi_used) *lepi_used = lepi;
+    route_set(CR_HS16, 0, a.OCpad, 0, 0, pool ? CR_E_POOL : (lepi ? CR_E_LDS : CR_E_REG));
     if (pool) {
       if (a.OCpad == 128) HS16(DT_BF16, 128, true, false);
       else HS16(DT_BF16, 64, true, false);
@@ -960,6 +963,7 @@ int conv3x3_hs_launch(const ConvArgs& a, int epi, hipStream_t s, bool* lepi_used
                     !(reinterpret_cast<uintptr_t>(a.out) & 15) &&
                     (!a.emask || (a.emask_ld % 8 == 0 && !(reinterpret_cast<uintptr_t>(a.emask) & 15)));
   if (lepi_used) *lepi_used = lepi;
+  route_set(CR_HS32, 0, a.OCpad, 0, 0, pool ? CR_E_POOL : (lepi ? CR_E_LDS : CR_E_REG));
 #define HS_LEPI(DT_, OCT_, NB1_) \
   hipLaunchKernelGGL((conv3x3_hs_kernel<DT_, OCT_, false, 3, NB1_, true>), grid, block, 0, s, a, tx, ty)
   if (pool) {
@@ -1008,6 +1012,8 @@ int conv3x3_stem_pool_launch(const ConvArgs& a, hipStream_t s) {
   const int tx = a.W / 16, ty = a.H / 16;
   const long long nwg = (long long)a.N * tx * ty;
   if (nwg > 0x7fffffffLL) return -2;
+  route_set(CR_HS16, 0, 64, 0, 0, CR_E_POOL);
+  g_route.cfg = 1;  // the fused stem
   hipLaunchKernelGGL((conv3x3_hs16_kernel<DT_BF16, 64, true, false, 3, false, true>), dim3((unsigned)nwg), dim3(256), 0,
                      s, a, tx, ty);
   return (int)hipGetLastError();

@@ -292,6 +292,7 @@ static int launch_cfg(const ConvArgs& a, hipStream_t s) {
   const int tiles_n = a.OCpad / BN;
   const long long nwg = (long long)tiles_m * tiles_n;
   if (nwg <= 0 || nwg > 0x7fffffffLL) return -2;
+  route_set(CR_IGEMM, BM, BN, 0, 0, CR_E_NONE);
   hipLaunchKernelGGL((conv_igemm_kernel<DT, WM, WN, FM, FN, AMODE, EPI, MASK_IN>), dim3((unsigned)nwg),
                      dim3(256), 0, s, a, tiles_n);
   return (int)hipGetLastError();

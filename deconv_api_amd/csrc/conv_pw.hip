@@ -149,6 +149,7 @@ int conv_pw_launch(const ConvArgs& a, hipStream_t s) {
   // DV_PW_WG_PER_CU: persistent workgroups per CU (2 by default: each holds 64 KiB of LDS ring)
   static const long long wpc = dv_ab_env("DV_PW_WG_PER_CU") ? std::max(1LL, std::atoll(dv_ab_env("DV_PW_WG_PER_CU"))) : 2;
   const unsigned G = (unsigned)std::min<long long>(tiles_total, wpc * cus);
+  route_set(CR_PW, BM, BN, 0, 0, CR_E_NONE);
   if (BN == 128) {
     if (a.dtype == DT_F16)
       hipLaunchKernelGGL((conv_pw_kernel<DT_F16, 4, 2, 2, 4>), dim3(G), dim3(512), 0, s, a, tiles_n, (int)tiles_total);

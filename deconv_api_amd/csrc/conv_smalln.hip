@@ -1044,6 +1044,7 @@ int conv3x3_c8_stream_launch(const ConvArgs& a, hipStream_t s) {
     return -4;
   const long long nwg = (long long)a.N * ((a.W + S8_W - 1) / S8_W);
   if (nwg <= 0 || nwg > 0x7fffffffLL) return -2;
+  route_set(CR_C8_STREAM, 0, 0, 0, 0, CR_E_NONE);
   if (a.H % 4 == 0 && a.W % S8_W == 0 && a.OC == 64)
     hipLaunchKernelGGL((conv3x3_c8_stream_kernel<4, true>), dim3((unsigned)nwg), dim3(256), 0, s, a);
   else
@@ -1071,6 +1072,7 @@ static int persist_cfg(const ConvArgs& a, hipStream_t s) {
     return n > 0 ? n : 256;
   }();
   const long long grid = std::min<long long>(ntiles, (long long)cus);
+  route_set(CR_HALO_V1, 0, 0, 0, 0, CR_E_PERSIST);
   hipLaunchKernelGGL((conv3x3_c64_persist_kernel<FN, EPI, UNPOOL>), dim3((unsigned)grid), dim3(512), 0, s, a);
   return (int)hipGetLastError();
 }
@@ -1089,6 +1091,7 @@ int conv3x3_pool_v3_launch(const ConvArgs& a, hipStream_t s) {
   }();
   const long long ntiles = (long long)a.N * ((a.H + TH - 1) / TH) * ((a.W + TW - 1) / TW);
   if (ntiles <= 0 || ntiles > 0x7fffffffLL) return -2;
+  route_set(CR_POOL_V3, 0, 0, 0, 0, CR_E_NONE);
   hipLaunchKernelGGL(conv3x3_c64_pool_v3_kernel, dim3((unsigned)std::min<long long>(ntiles, cus)), dim3(256), 0, s, a);
   return (int)hipGetLastError();
 }
@@ -1110,6 +1113,7 @@ int conv3x3_halo_launch(const ConvArgs& a, int unpool, int epi, hipStream_t s, b
     }();
     const long long ntiles = (long long)a.N * ((a.H + TH - 1) / TH) * ((a.W + TW - 1) / TW);
     if (ntiles <= 0 || ntiles > 0x7fffffffLL) return -2;
+    route_set(CR_HALO_V2, 0, 0, 0, 0, CR_E_NONE);
     hipLaunchKernelGGL(conv3x3_unpool_c64_v2_kernel<false>, dim3((unsigned)std::min<long long>(ntiles, cus)), dim3(512), 0, s,
                        a);
     return (int)hipGetLastError();
@@ -1118,6 +1122,7 @@ int conv3x3_halo_launch(const ConvArgs& a, int unpool, int epi, hipStream_t s, b
     const long long nwg = (long long)a.N * ((a.W + ST_W - 1) / ST_W);
     if (nwg <= 0 || nwg > 0x7fffffffLL) return -2;
     const int P = stream_variant();
+    route_set(CR_HALO_V1, 0, 0, 0, 0, CR_E_STRIPS);
     if (stats_done) *stats_done = a.stats != nullptr;
 #define DV_S2(PP, E)                                                                                               \
   do {                                                                                                             \

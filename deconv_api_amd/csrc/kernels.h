@@ -9,10 +9,11 @@
 // Runtime A/B switch of a measured alternative (deconv_api_amd/knobs.py ABLATION): the variable is read
 // only when DV_ABLATIONS=1, so a serving / benchmark process takes one dispatch per shape whatever its
 // environment holds; tools/*_ab.py and the variant tests set DV_ABLATIONS=1. (Host code only.)
-static inline const char* dv_ab_env(const char* name) {
+static inline bool dv_ablations_on() {
   const char* on = std::getenv("DV_ABLATIONS");
-  return (on != nullptr && on[0] == '1' && on[1] == 0) ? std::getenv(name) : nullptr;
+  return on != nullptr && on[0] == '1' && on[1] == 0;
 }
+static inline const char* dv_ab_env(const char* name) { return dv_ablations_on() ? std::getenv(name) : nullptr; }
 
 namespace dv {
 
@@ -106,6 +107,37 @@ struct ConvGroup {
   int tiles_n[kGroupMax];
   int n;
 };
+
+// Route report: which kernel the last conv() call on this thread launched (bindings.cpp conv_route()).
+// A plain thread-local record the launchers fill where they pick the kernel (a few integer stores, no
+// getenv, no formatting on the launch path); bindings.cpp clears it at entry and formats it on request.
+// Tests assert it, so a threshold change or another CU count cannot silently turn a kernel's test into
+// a test of its fallback.
+enum ConvRouteKind : int {
+  CR_NONE = 0, CR_IGEMM, CR_HALO_V1, CR_HALO_V2, CR_POOL_V3, CR_C8_STREAM, CR_HS16, CR_HS32, CR_PW, CR_DMA,
+  CR_KW3, CR_KW3P, CR_GROUP,
+};
+enum ConvRouteEpi : int {
+  CR_E_NONE = 0, CR_E_REG, CR_E_LDS, CR_E_UNPOOL, CR_E_POOL, CR_E_STRIPS, CR_E_PERSIST,
+  CR_E_POOL_T, CR_E_POOL_LDS,  // LDS-DMA pooled-max epilogues: DPP-transposed 8-B stores / staged through LDS
+};
+enum ConvRouteFlag : int {
+  CR_F_SK = 1,        // KW3P stream-K
+  CR_F_OCSPLIT = 2,   // halo-stream: two launches over the output-channel halves
+  CR_F_TAIL = 4,      // KW3 / KW3P full rounds + a 128 x 128 DMA tail launch from row m_base
+  CR_F_UNPOOL = 8,    // pre-pass: the unpooled input was materialized (unpool2x2)
+  CR_F_RELU_COPY = 16,  // pre-pass: dense ReLU copy of the input
+  CR_F_MASK = 32,     // ReLU-masked A operand (dma_mask_bn)
+};
+struct ConvRoute {
+  int kind, bm, bn, stages, ksplit, epi, flags, m_base, cfg;
+};
+extern __thread ConvRoute g_route;  // defined in conv_dma.hip
+// A launcher records its WHOLE choice (nothing of an earlier launcher that recorded and then declined, or of
+// the first half of a two-launch form, survives); only the pre-pass flags bindings.cpp set before it stay.
+static inline void route_set(int kind, int bm, int bn, int stages, int ksplit, int epi, int flags = 0) {
+  g_route = ConvRoute{kind, bm, bn, stages, ksplit, epi, (g_route.flags & (CR_F_UNPOOL | CR_F_RELU_COPY)) | flags, 0, 0};
+}
 
 int conv_igemm_launch(const ConvArgs& a, int amode, int epi, hipStream_t stream);
 // LDS-DMA variant (FWD / TRANSPOSE, no mask): 8-wave 128x64-per-wave tiles

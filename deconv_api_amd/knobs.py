@@ -40,7 +40,7 @@ RUNTIME = {
 
 ABLATION = {
     # conv_dma_impl.h: KW3P (shared-kw-tap implicit GEMM) variants and tile choices
-    "DV_KW3": "KW3 kernel off / forced (tests: small shapes with many borders)",
+    "DV_KW3": "KW3 kernel off / forced, ahead of the small-problem tiles too (tests: small shapes with many borders)",
     "DV_KW3_VAR": "KW3 main-loop variant (profiles/kw3_variants_r3.txt, kw3_staging_ablation_r5.txt)",
     "DV_KW3_TILE": "KW3P tile shape (profiles/kw3_ab_r4.txt)",
     "DV_KW3_SK": "stream-K on every eligible grid, not only short ones (profiles/kw3_skall_ab_r5.txt)",
@@ -51,7 +51,7 @@ ABLATION = {
     "DV_ALLOW_WRONG_ABLATION": "timing-only variants whose outputs are wrong (tools/kw3_ab.py, tools/tail_ab.py)",
     "DV_NO_AUTO_CFG": "size-based DMA tile choice only (docs/KERNELS.md)",
     "DV_SMALL_TILE_KMIN": "K threshold of the 64x64 small-problem tile",
-    "DV_NO_SPLITK": "split-K off (tools/small_conv_latency.py)",
+    "DV_NO_SPLITK": "split-K off, latched at the first DMA conv (tools/small_conv_latency.py; tests: dma_tune(0, 1))",
     "DV_NO_SMALL_SPLITK": "small-problem split-K off",
     "DV_SMALL_SPLITK_MN": "M x N ceiling of the small-problem split-K",
     # bindings.cpp routing

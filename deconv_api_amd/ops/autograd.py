@@ -229,7 +229,8 @@ def dgrad_strided_into(unit: ConvUnit, gy, in_hw, out: torch.Tensor, accumulate:
                        emask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``out`` (=|+=) input gradient of a strided conv, zeroed where ``emask`` <= 0: one transposed
     conv on the LDS-DMA kernel when small (``strided_direct``), else the sub-pixel / col2im path
-    plus one elementwise pass."""
+    plus one elementwise pass. With ``accumulate`` the mask applies to the SUM, as in the kernels
+    (conv2d's epilogue order; csrc/pool.hip subpixel_merge_kernel): out = (out + grad) * (emask > 0)."""
     if strided_direct(unit, gy, in_hw):
         return conv2d(gy, unit.bwd, stride=unit.stride, pad=unit.pad, relu=False, in_mode="transpose",
                       out_hw=in_hw, use_bias=False, out=out, accumulate=accumulate, emask=emask)
@@ -237,9 +238,11 @@ def dgrad_strided_into(unit: ConvUnit, gy, in_hw, out: torch.Tensor, accumulate:
         # parity-class GEMMs merged straight into ``out`` with the accumulate and the mask in the same pass
         return _subpixel_dgrad(gy, None, unit, in_hw, out=out, accumulate=accumulate, emask=emask)
     r = _dgrad_strided(unit, gy, None, in_hw)
+    if accumulate:
+        r = out + r
     if emask is not None:
         r = torch.ops.aten.threshold_backward(r, emask, 0)
-    return out.add_(r) if accumulate else out.copy_(r)
+    return out.copy_(r)
 
 
 def _dgrad_strided(unit: ConvUnit, gy, mask, in_hw):

@@ -230,7 +230,12 @@ def conv2d(x: torch.Tensor, cw: ConvWeights, *, stride: int = 1, pad=None, relu:
     the pooled map [N, H/2, W/2, C] and ``code`` its switch codes ([N/code_div, H/2, W/2, C]).
     epilogue 'pool' returns ``(pooled, code)``; otherwise the output tensor.
     ``res``: fused residual (ResNet block tail), out = [ReLU](conv + bias + res), ReLU after the add;
-    ``emask`` (with ``res``): the result is zeroed where emask <= 0.
+    ``emask``: the result is zeroed where emask <= 0 (0.0 and -0.0 included).
+    Epilogue order, the kernels' (csrc/conv_dma_impl.h epilogue_res / epilogue_lds, conv_dma.hip
+    splitk_reduce_kernel): v = conv + bias; ReLU (without ``res``); += ``res``; += the old ``out``
+    (``accumulate``); ReLU (with ``res``); zero where ``emask`` <= 0 LAST, so with ``accumulate`` and
+    ``emask`` the old output is masked too: out = (out + conv) * (emask > 0), the input gradient of a
+    ReLU output summed over its consumers (ops/autograd.py dgrad_strided_into, ops/inception.py).
     ``stats`` (GPU, fp32 epilogue): fp64 [N / stats_div, 2] receives {sum, sum of squares} of each
     group of ``stats_div`` output images (the single-pass mosaic deprocess consumes it).
     ``unpool_out``: switch codes [N / unpool_div, OH, OW, OC]; the result is max-unpooled in the
@@ -320,7 +325,7 @@ def _conv2d_ref(x, cw, N, H, W, C, OH, OW, OC, stride, pad, relu, relu_in, in_mo
         y = torch.cat([y[..., :relu_cols].clamp_min(0), y[..., relu_cols:]], dim=-1)
     elif relu:
         y = y.clamp_min(0)
-    if emask is not None:
+    if emask is not None and not (accumulate and out is not None):
         y = y * (emask.float() > 0)
     if epilogue == "pool":
         y = y.to(dtype).float()  # pool on stored-precision values, like the fused GPU epilogue
@@ -332,8 +337,10 @@ def _conv2d_ref(x, cw, N, H, W, C, OH, OW, OC, stride, pad, relu, relu_in, in_mo
         return pv, pc.contiguous()
     odt = torch.float32 if epilogue == "f32" else dtype
     if out is not None:
-        if accumulate:
+        if accumulate:  # accumulate, then mask: the kernels' order (conv2d docstring)
             y = y + out.float()
+            if emask is not None:
+                y = y * (emask.float() > 0)
         out.copy_(y.to(out.dtype))
         return out
     return y.to(odt).contiguous()

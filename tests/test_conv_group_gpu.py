@@ -53,7 +53,10 @@ def _problems(dt):
 @pytest.mark.parametrize("dt", [torch.bfloat16, torch.float16])
 def test_grouped_launch_bit_identical(native_lib, dt):
     probs = _problems(dt)
-    ref = [ops.conv2d(x, cw, **kw) for x, cw, kw in probs]
+    ref = []
+    for x, cw, kw in probs:
+        ref.append(ops.conv2d(x, cw, **kw))
+        assert ops.native.lib().conv_route() == "dma 64x64 st3 ks1", ops.native.lib().conv_route()  # the same tile program
     acc_base = torch.randn(*ref[1].shape, generator=torch.Generator().manual_seed(9)).to(dt).cuda()
     want_acc = acc_base.clone()
     ops.conv2d(probs[1][0], probs[1][1], out=want_acc, accumulate=True, **probs[1][2])
@@ -65,6 +68,7 @@ def test_grouped_launch_bit_identical(native_lib, dt):
     try:
         for (x, cw, kw), o in zip(probs, outs):
             ops.conv2d(x, cw, out=o, **kw)
+            assert lib.conv_route() == "group cfg8", lib.conv_route()  # recorded, not launched
         ops.conv2d(probs[1][0], probs[1][1], out=got_acc, accumulate=True, **probs[1][2])
     finally:
         n = lib.conv_group_end()
