@@ -152,7 +152,7 @@ int64_t conv(Tensor x, Tensor w, c10::optional<Tensor> bias, Tensor out, c10::op
              int64_t epi, int64_t impl, c10::optional<Tensor> res, c10::optional<Tensor> emask,
              c10::optional<Tensor> stats, int64_t stats_div, c10::optional<Tensor> ucode, int64_t ucode_div,
              int64_t relu_cols, c10::optional<Tensor> out2, int64_t split_col, c10::optional<Tensor> obits,
-             c10::optional<Tensor> ebits) {
+             c10::optional<Tensor> ebits, c10::optional<Tensor> w_kw3) {
   TORCH_CHECK(g.size() == 23, "conv: geometry vector must have 23 entries");
   dv::g_route = dv::ConvRoute{};  // route report of this call (conv_route()); the launchers fill it
   check_cuda(x, "x");
@@ -188,6 +188,23 @@ int64_t conv(Tensor x, Tensor w, c10::optional<Tensor> bias, Tensor out, c10::op
   a.w = reinterpret_cast<const uint16_t*>(w.data_ptr());
   a.x_elems = avail_bytes(x) / 2;
   a.out_elems = avail_bytes(out) / (int64_t)out.element_size();
+  // packed KW3 B image (ops/conv.py kw3_pack; the KW3 / KW3P kernels stage B from it when set).
+  // DV_KW3_BPACK=0: the strided w_gemm reads (A/B; read per call)
+  if (w_kw3.has_value()) {
+    check_cuda(*w_kw3, "w_kw3");
+    const int64_t pn = (int64_t)a.OCpad * 9 * a.C;
+    TORCH_CHECK(w_kw3->scalar_type() == dt && w_kw3->device() == w.device() && w_kw3->is_contiguous(),
+                "conv: w_kw3 must be contiguous, of w's dtype, on w's device");
+    TORCH_CHECK(a.KH == 3 && a.KW == 3 && a.C % 32 == 0 && a.OCpad % 128 == 0 && w_kw3->numel() == pn,
+                "conv: w_kw3 must hold OCpad*9*C elements of a 3x3 conv with C % 32 == 0, OCpad % 128 == 0");
+    TORCH_CHECK(pn * 2 < (1LL << 31), "conv: w_kw3 must be smaller than 2^31 bytes");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(w_kw3->data_ptr()) % 16 == 0, "conv: w_kw3 must be 16-byte aligned");
+    const char* bp = dv_ab_env("DV_KW3_BPACK");
+    if (!(bp && std::strcmp(bp, "0") == 0)) {
+      a.wp = reinterpret_cast<const uint16_t*>(w_kw3->data_ptr());
+      a.wp_elems = avail_bytes(*w_kw3) / 2;
+    }
+  }
 
   // input extent
   int64_t in_pix = (int64_t)a.N * a.H * a.W;
@@ -1510,8 +1527,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("res") = py::none(), py::arg("emask") = py::none(), py::arg("stats") = py::none(),
         py::arg("stats_div") = 1, py::arg("ucode") = py::none(), py::arg("ucode_div") = 1,
         py::arg("relu_cols") = 0, py::arg("out2") = py::none(), py::arg("split_col") = 0,
-        py::arg("obits") = py::none(), py::arg("ebits") = py::none());
+        py::arg("obits") = py::none(), py::arg("ebits") = py::none(), py::arg("w_kw3") = py::none());
   m.def("conv_route", &conv_route, "kernel the last conv call on this thread launched (route report)");
+  m.def("conv_bpack", [] { return dv::g_route.bpack != 0; },
+        "whether the last conv call on this thread staged its weights from the packed KW3 image (w_kw3)");
   m.def("conv_group_begin", &conv_group_begin, "start recording groupable small-problem convs (this thread)");
   m.def("conv_group_pause", [](bool p) { g_group_paused = p; }, "suspend / resume recording (dependent convs)");
   m.def("conv_group_end", &conv_group_end, "launch the recorded convs as grouped kernels; returns the launch count");

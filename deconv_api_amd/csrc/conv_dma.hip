@@ -8,7 +8,7 @@ namespace dv {
 // Tuning override (tools/tune_dma.py): force tile config `g_cfg` (> 0) and split-K factor
 // `g_ks` (> 0) for every DMA conv launch until reset to 0. Host-side globals, set between launches.
 int g_cfg = 0, g_ks = 0;
-__thread ConvRoute g_route = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // route report (kernels.h)
+__thread ConvRoute g_route = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // route report (kernels.h)
 void conv_dma_tune(int cfg, int ks) {
   g_cfg = cfg;
   g_ks = ks;

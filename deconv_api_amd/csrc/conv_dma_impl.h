@@ -40,6 +40,13 @@ __device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, uint8_t* lds_
   __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds_dst, 16, voff, 0, 0, 0);
 }
 
+// dma16 with the address split into a per-lane part that stays in one VGPR for the whole launch and a
+// wave-uniform part in the instruction's scalar-offset operand: no per-instruction address VALU
+__device__ __forceinline__ void dma16_s(__amdgpu_buffer_rsrc_t rsrc, uint8_t* lds_dst, uint32_t voff, uint32_t soff) {
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)lds_dst, 16, voff, __builtin_amdgcn_readfirstlane(soff),
+                                           0, 0);
+}
+
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, uint64_t bytes) {
   const uint32_t nrec = bytes > 0x7FFFFFF0ull ? 0x7FFFFFF0u : (uint32_t)bytes;
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, (int)nrec, 0x00020000);
@@ -965,6 +972,30 @@ __device__ __forceinline__ int kw3_swz(int row) { return ((row >> 2) & 1) << 1; 
 constexpr int kw3_a_i(int bm) { return bm == 256 ? 4 : 5; }
 constexpr int kKw3Pad = 8;  // zero slots between image rows: a row jump is +9 slots = +1 (mod 8)
 constexpr int kKw3DefaultVar = 2;
+
+// Where issue() finds the B sub-tile (kh, cc, kw, 16-row block rb) of the tile at column n0: byte offset
+// lane + kh s_kh + cc s_cc + n0 s_n0 + kw s_kw + rb s_rb from base. Every term but ``lane`` is wave-uniform
+// and goes into the DMA's scalar offset (dma16_s).
+//   strided (a.wp == nullptr): w[OCpad][Kpad]. A wave-instruction covers 16 rows x 64 B, each piece half of a
+//     128-B line whose other half belongs to the next channel chunk, three K steps later.
+//   packed (a.wp, ops/conv.py kw3_pack): the stage's own byte image, piece[step = 3 cc + kh][kw][rb] of 1 KiB,
+//     lane l at 16 l. A wave-instruction covers eight whole lines and a sub-tile is BN * 64 contiguous bytes.
+// Both put the same bytes in LDS (the packer applies the lane -> (row, swizzled chunk) map below).
+struct Kw3BSrc {
+  const void* base;
+  uint64_t bytes;
+  uint32_t lane, s_kh, s_cc, s_n0, s_kw, s_rb;
+};
+__device__ __forceinline__ Kw3BSrc kw3_bsrc(const ConvArgs& a, int lane) {
+  if (a.wp != nullptr) {
+    const uint32_t rbs = (uint32_t)a.OCpad >> 4;
+    return Kw3BSrc{a.wp, (uint64_t)a.OCpad * 9 * a.C * 2, (uint32_t)lane * 16u, 3072u * rbs, 9216u * rbs, 64u,
+                   1024u * rbs, 1024u};
+  }
+  const uint32_t lrow = (uint32_t)lane >> 2, lchunk = ((uint32_t)lane & 3u) ^ (uint32_t)kw3_swz((int)lrow);
+  return Kw3BSrc{a.w, (uint64_t)a.OCpad * a.Kpad * 2, (lrow * (uint32_t)a.Kpad + lchunk * 8u) * 2u, 6u * (uint32_t)a.C,
+                 64u, 2u * (uint32_t)a.Kpad, 2u * (uint32_t)a.C, 32u * (uint32_t)a.Kpad};
+}
 }  // namespace
 
 // BM_ x BN_: 256 x 256 (8 waves of 128 x 64) or 512 x 128 (8 waves of 128 x 64: the same per-wave
@@ -1002,7 +1033,8 @@ __global__ void __launch_bounds__(512) conv_dma_kw3_kernel(const ConvArgs a, int
   const long long x_total = (long long)a.N * img_elems;
   const __amdgpu_buffer_rsrc_t xr =
       make_rsrc(a.x + (long long)n_base * img_elems, (uint64_t)(x_total - (long long)n_base * img_elems) * 2);
-  const __amdgpu_buffer_rsrc_t wr = make_rsrc(a.w, (uint64_t)a.OCpad * a.Kpad * 2);
+  const Kw3BSrc bs = kw3_bsrc(a, lane);  // packed image (a.wp) or the strided a.w
+  const __amdgpu_buffer_rsrc_t wr = make_rsrc(bs.base, bs.bytes);
 
   // padded coordinate of output row m (global image row R = m / W, W + 8 slots per row: 4 zero
   // slots on each side, so consecutive output rows across a row boundary sit 9 slots apart, the
@@ -1044,13 +1076,13 @@ __global__ void __launch_bounds__(512) conv_dma_kw3_kernel(const ConvArgs a, int
           ok ? ((uint32_t)(r_pix[u] + (kh - 1) * W) * (uint32_t)a.x_ld + (uint32_t)(cc * 32 + lchunk * 8)) * 2u : kOOB;
       dma16(xr, As + (u * NW + wave) * 1024, voff);
     }
+    const uint32_t b0 = (uint32_t)kh * bs.s_kh + (uint32_t)cc * bs.s_cc + (uint32_t)n0 * bs.s_n0;
 #pragma unroll
     for (int u = 0; u < B_I; ++u) {
-      const int v = u * NW + wave;  // kw sub-tile v >> 4, rows (v & 15) * 16 + lrow
-      const int kw = v / (BN / 16), brow = (v % (BN / 16)) * 16 + lrow;
-      const uint32_t voff =
-          ((uint32_t)(n0 + brow) * (uint32_t)a.Kpad + (uint32_t)((kh * 3 + kw) * C + cc * 32 + lchunk * 8)) * 2u;
-      dma16(wr, Bs + v * 1024, voff);
+      const int v = u * NW + wave;  // kw sub-tile v / (BN / 16), its 16-row block v % (BN / 16)
+      const uint32_t so = b0 + (uint32_t)(v / (BN / 16)) * bs.s_kw + (uint32_t)(v % (BN / 16)) * bs.s_rb;
+      if (a.wp == nullptr || DV_BOUNDS((long long)((so + bs.lane) >> 1), 8, a.wp_elems, "kw3 packed B"))
+        dma16_s(wr, Bs + v * 1024, bs.lane, so);
     }
   };
 
@@ -1210,7 +1242,8 @@ __global__ void __launch_bounds__(512) conv_dma_kw3p_kernel(const ConvArgs a, in
   const int H = a.H, W = a.W, C = a.C, HW = a.H * a.W, Wp = a.W + kKw3Pad;
   const long long img_elems = (long long)HW * a.x_ld;
   const long long x_total = (long long)a.N * img_elems;
-  const __amdgpu_buffer_rsrc_t wr = make_rsrc(a.w, (uint64_t)a.OCpad * a.Kpad * 2);
+  const Kw3BSrc bs = kw3_bsrc(a, lane);  // packed image (a.wp) or the strided a.w
+  const __amdgpu_buffer_rsrc_t wr = make_rsrc(bs.base, bs.bytes);
   const __amdgpu_buffer_rsrc_t orr = make_rsrc(a.out, (uint64_t)a.out_elems * 2);
   const int lrow = lane >> 2;
   const int lchunk = (lane & 3) ^ kw3_swz(lrow);
@@ -1272,13 +1305,13 @@ __global__ void __launch_bounds__(512) conv_dma_kw3p_kernel(const ConvArgs a, in
       dma16(xr, As + (u * NW + wave) * 1024, voff);
     }
     if (SV == 4 && abl_skip) return;
+    const uint32_t b0 = (uint32_t)kh * bs.s_kh + (uint32_t)cc * bs.s_cc + (uint32_t)n0 * bs.s_n0;
 #pragma unroll
     for (int u = 0; u < B_I; ++u) {
-      const int vv = u * NW + wave;
-      const int kw = vv / (BN / 16), brow = (vv % (BN / 16)) * 16 + lrow;
-      const uint32_t voff =
-          ((uint32_t)(n0 + brow) * (uint32_t)a.Kpad + (uint32_t)((kh * 3 + kw) * C + cc * 32 + lchunk * 8)) * 2u;
-      dma16(wr, Bs + vv * 1024, voff);
+      const int vv = u * NW + wave;  // kw sub-tile vv / (BN / 16), its 16-row block vv % (BN / 16)
+      const uint32_t so = b0 + (uint32_t)(vv / (BN / 16)) * bs.s_kw + (uint32_t)(vv % (BN / 16)) * bs.s_rb;
+      if (a.wp == nullptr || DV_BOUNDS((long long)((so + bs.lane) >> 1), 8, a.wp_elems, "kw3p packed B"))
+        dma16_s(wr, Bs + vv * 1024, bs.lane, so);
     }
   };
 
@@ -1744,6 +1777,7 @@ static int kw3_try(const ConvArgs& a, hipStream_t s, int tiles_m_limit = 0) {
         constexpr int U = decltype(em)::value;
         const unsigned g = (unsigned)(nwg < (long long)num_cus() ? nwg : (long long)num_cus());
         route_set(CR_KW3P, BM, BN, 0, 0, U == 1 ? CR_E_UNPOOL : (U == 2 ? CR_E_LDS : CR_E_REG));
+        g_route.bpack = a.wp != nullptr;  // B staged from the packed image (bindings.cpp conv_bpack())
         if constexpr (DT == DT_BF16) {
           if (var == 10) {
             hipLaunchKernelGGL((conv_dma_kw3p_kernel<DT, BN, BM, U, 1>), dim3(g), dim3(512), 0, s, a, tiles_n, (int)nwg, kw3p_pre());
@@ -1803,6 +1837,7 @@ static int kw3_try(const ConvArgs& a, hipStream_t s, int tiles_m_limit = 0) {
         return launch_p(std::integral_constant<int, 1>{});
     }
     route_set(CR_KW3, BM, BN, 0, 0, CR_E_NONE);
+    g_route.bpack = a.wp != nullptr;
     if constexpr (DT == DT_BF16 && EPI == CONV_E_BF16) {
       if (var == 8 || var == 9) {
         if (var == 8)

@@ -94,6 +94,12 @@ struct ConvArgs {
   // tap * 8 + c of the 8-channel RGB input) and its fp32 bias bias2
   const float* bias2;
   int kpad2;
+  // optional (KW3 / KW3P kernels): the 3x3 weights as the byte image their B stages hold, built once at
+  // weight-load time (ops/conv.py kw3_pack): 1-KiB pieces piece[step = cc*3 + kh][kw][row block of 16], lane l
+  // of a piece = 8 elements of row rb*16 + (l >> 2) at w column (kh*3 + kw)*C + cc*32 + 8*((l & 3) ^ swizzle);
+  // OCpad*9*C elements (no K padding). nullptr: absent or switched off (DV_KW3_BPACK=0), B is read from w
+  const uint16_t* wp;
+  long long wp_elems;     // storage extent of wp (DV_DEBUG bounds checks, as x_elems)
 };
 // KW3P stream-K: fp32 partial-tile slot per workgroup (BM x BN = 65536 for both KW3P tile shapes)
 constexpr long long kSkSlotFloats = 256LL * 256LL;
@@ -131,6 +137,7 @@ enum ConvRouteFlag : int {
 };
 struct ConvRoute {
   int kind, bm, bn, stages, ksplit, epi, flags, m_base, cfg;
+  int bpack;  // KW3 / KW3P: B was staged from the packed image (not part of the route string; conv_bpack())
 };
 extern __thread ConvRoute g_route;  // defined in conv_dma.hip
 // A launcher records its WHOLE choice (nothing of an earlier launcher that recorded and then declined, or of

@@ -45,6 +45,7 @@ ABLATION = {
     "DV_KW3_TILE": "KW3P tile shape (profiles/kw3_ab_r4.txt)",
     "DV_KW3_SK": "stream-K on every eligible grid, not only short ones (profiles/kw3_skall_ab_r5.txt)",
     "DV_KW3P_EPI": "register-layout 8-B epilogue instead of the LDS-staged 16-B one (profiles/kw3_epi_ab_r5.txt)",
+    "DV_KW3_BPACK": "0: KW3 weights from the strided w_gemm, not the packed image (profiles/kw3_bpack_ab_r7.txt)",
     "DV_KW3P_NO_PRE": "no step-1 DMA ahead of the epilogue (profiles/kw3_pre_ab_r5.txt)",
     "DV_KW3P_UNP_NT": "plain instead of non-temporal unpool stores (profiles/bench_c2_r5_unp_nt_ab.txt)",
     "DV_NO_KW3P_UNPOOL": "unpool-out conv-downs off KW3P (profiles/kw3_store_ablation_r5.txt)",

@@ -61,6 +61,44 @@ def oc_pad(oc: int) -> int:
     return 16
 
 
+def kw3_swz(row: int) -> int:
+    """16-B chunk swizzle of LDS row ``row`` in the KW3 kernels' 64-B rows (csrc/conv_dma_impl.h kw3_swz)."""
+    return ((row >> 2) & 1) << 1
+
+
+def kw3_packable(kh: int, kw: int, cin: int, ocpad: int, kind: str = "fwd") -> bool:
+    """Convs whose weights get the packed KW3 image: the shapes the shared-kw-tap kernels take (3x3 forward
+    gather, whole 32-channel chunks, whole 128-column tiles), below the 2^31-byte buffer range."""
+    return kind == "fwd" and kh == 3 and kw == 3 and cin % 32 == 0 and ocpad % 128 == 0 and ocpad * 9 * cin * 2 < 2 ** 31
+
+
+def kw3_pack(w_gemm: torch.Tensor, cin: int) -> torch.Tensor:
+    """The byte image the KW3 / KW3P kernels' B stages hold, from ``w_gemm[OCpad, Kpad]`` of a 3x3 conv.
+
+    1-KiB pieces in the order ``piece[step][kw][rb]``, ``step = cc*3 + kh`` (kh innermost, as the kernels walk
+    K), ``rb`` over the OCpad/16 blocks of 16 rows. Inside a piece, lane ``l``'s 16 bytes (8 elements) are row
+    ``rb*16 + (l >> 2)``, columns ``(kh*3 + kw)*C + cc*32 + 8*((l & 3) ^ kw3_swz(l >> 2))`` of ``w_gemm``:
+    exactly what the strided per-lane DMA gathers, so a tile's (step, kw) sub-tile is ``BN*64`` contiguous
+    bytes (whole 128-B lines) at piece ``(step*3 + kw)*(OCpad/16) + n0/16``. OCpad*9*C elements, no K padding.
+    """
+    ocpad = w_gemm.shape[0]
+    assert kw3_packable(3, 3, cin, ocpad) and w_gemm.shape[1] >= 9 * cin
+    t = w_gemm[:, : 9 * cin].reshape(ocpad // 16, 16, 3, 3, cin // 32, 4, 8)  # rb, r, kh, kw, cc, chunk, e
+    t = t.permute(4, 2, 3, 0, 1, 5, 6)                                        # cc, kh, kw, rb, r, chunk, e
+    r = torch.arange(16, device=w_gemm.device)
+    src = torch.arange(4, device=w_gemm.device)[None, :] ^ (((r >> 2) & 1) << 1)[:, None]  # [r, l & 3] -> chunk
+    return t[:, :, :, :, r[:, None], src, :].contiguous().reshape(-1)
+
+
+def kw3_unpack(w_kw3: torch.Tensor, ocpad: int, cin: int) -> torch.Tensor:
+    """Inverse of ``kw3_pack``: ``w_gemm[:, :9*cin]`` from the packed image."""
+    t = w_kw3.reshape(cin // 32, 3, 3, ocpad // 16, 16, 4, 8)
+    r = torch.arange(16, device=w_kw3.device)
+    src = torch.arange(4, device=w_kw3.device)[None, :] ^ (((r >> 2) & 1) << 1)[:, None]
+    t = t[:, :, :, :, r[:, None], src, :]  # the swizzle is an involution
+    return t.permute(3, 4, 1, 2, 0, 5, 6).reshape(ocpad, 9 * cin).contiguous()
+
+
 @dataclass
 class ConvWeights:
     """A conv in torch OIHW form plus its gfx950 GEMM packing.
@@ -76,6 +114,7 @@ class ConvWeights:
     kind: str = "fwd"
     w_gemm: Optional[torch.Tensor] = None
     bias_pad: Optional[torch.Tensor] = None
+    w_kw3: Optional[torch.Tensor] = None  # packed KW3 B image of an eligible 3x3 conv (kw3_pack), else None
 
     @property
     def KH(self) -> int:
@@ -127,6 +166,10 @@ class ConvWeights:
         cw = ConvWeights(w_oihw, bias, self.kind)
         if device.type == "cuda":
             cw.w_gemm = self.gemm_matrix().to(device=device, dtype=dtype).contiguous()
+            # eagerly, never at first use: a graph capture must not allocate or pack. Costs the weights'
+            # size again (about 58 MB for VGG16's forward + deconv 3x3 convs, docs/KERNELS.md round 7)
+            if kw3_packable(self.KH, self.KW, self.cin, self.OCpad, self.kind):
+                cw.w_kw3 = kw3_pack(cw.w_gemm, self.cin)
             if bias is not None:
                 bp = torch.zeros(self.OCpad, dtype=torch.float32)
                 bp[: self.cout] = self.bias.float().cpu()
@@ -460,7 +503,7 @@ def _conv2d_hip(x, cw, N, H, W, C, OH, OW, OC, stride, pad, relu, relu_in, in_mo
     _tls.bits = lib.conv(x, cw.w_gemm, bias, out, out_code, code, mask, geom, AMODE[in_mode], EPI[epilogue],
                          IMPL["dma"] if dma_only else IMPL[_policy["impl"]],  # DMA-only epilogue features
                          res, emask, stats, stats_div, unpool_out, unpool_div, relu_cols, out2, split_col,
-                         obits, ebits)
+                         obits, ebits, cw.w_kw3)
     if epilogue == "pool":
         return out, out_code
     return out

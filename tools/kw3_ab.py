@@ -7,6 +7,12 @@ VAR 0 (KW3) / 2 (persistent KW3P, the default) are real kernels (their outputs a
 accumulation order is the same); 8 (no epilogue stores) and 9 (no K loop) are ablations that price the epilogue and the
 prologue + epilogue of a tile. Prints one JSON line per (case, variant) with the median and min
 time over rounds and the conv TF/s.
+
+    python tools/kw3_ab.py --vars 2 --bpack 0,1
+
+--bpack 0,1 adds the B-source axis: 1 = weights staged from the packed, line-contiguous image (ConvWeights.w_kw3,
+the default), 0 = the strided w_gemm reads (DV_KW3_BPACK=0). Both are real kernels with bit-equal outputs; they
+interleave with the variants in the same rounds.
 """
 import argparse
 import json
@@ -47,11 +53,13 @@ def main():
     ap.add_argument("--cases", default=",".join(CASES))
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--bpack", default="1", help="B source axis: 1 packed image (default), 0 strided w_gemm; e.g. 0,1")
     a = ap.parse_args()
     os.environ.setdefault("DV_ALLOW_WRONG_ABLATION", "1")  # VAR 8 / 9 are wrong-output timing ablations
     ops.native.load()
     dev = torch.device("cuda", 0)
-    variants = [int(v) for v in a.vars.split(",")]
+    bpacks = [int(b) for b in a.bpack.split(",")]
+    variants = [(int(v), b) for v in a.vars.split(",") for b in bpacks]  # (VAR, B source)
     g = torch.Generator(device=dev).manual_seed(0)
     for case in a.cases.split(","):
         N, H, W, C, OC = CASES[case]
@@ -62,7 +70,12 @@ def main():
         unp = case.endswith("unp")
         code = torch.randint(0, 4, (N // 4, H, W, OC), device=dev, dtype=torch.uint8, generator=g) if unp else None
 
-        def run(v):
+        def run(vb):
+            v, bp = vb
+            if bp:
+                os.environ.pop("DV_KW3_BPACK", None)
+            else:
+                os.environ["DV_KW3_BPACK"] = "0"
             # 2: KW3P as selected (stream-K where it applies, step-1 DMA ahead of the epilogue stores);
             # 12: whole tiles (DV_NO_KW3_SK=1); 13: whole tiles without the early DMA (+ DV_KW3P_NO_PRE=1);
             # 14: stream-K without the early DMA; 15: whole tiles with the register-transposed 8-B store epilogue;
@@ -87,14 +100,14 @@ def main():
             else:
                 os.environ.pop("DV_KW3_TILE", None)
             if unp:  # a fresh unpooled output per call (as the engine does)
-                out[v] = ops.conv2d(x, cw, relu=True, use_bias=False, unpool_out=code, unpool_div=4)
-                return out[v]
-            return ops.conv2d(x, cw, relu=True, use_bias=False, out=out[v])
+                out[vb] = ops.conv2d(x, cw, relu=True, use_bias=False, unpool_out=code, unpool_div=4)
+                return out[vb]
+            return ops.conv2d(x, cw, relu=True, use_bias=False, out=out[vb])
 
         for v in variants:  # warm up every variant (and check the real ones agree)
             run(v)
         torch.cuda.synchronize()
-        real = [v for v in variants if v < 8 or v in (11, 12, 13, 14, 15, 16, 22)]
+        real = [v for v in variants if v[0] < 8 or v[0] in (11, 12, 13, 14, 15, 16, 22)]
         for v in real[1:]:
             same = torch.equal(out[v], out[real[0]])
             if not same:  # stream-K vs whole tiles: split tiles round differently
@@ -102,7 +115,8 @@ def main():
                 same = float(d.max()) <= 2 ** -6 * float(out[real[0]].float().abs().max())
             if not same:
                 d = (out[v].float() - out[real[0]].float()).abs().max().item()
-                print(json.dumps({"case": case, "var": v, "equal_to": real[0], "equal": False, "maxdiff": d}),
+                print(json.dumps({"case": case, "var": v[0], "bpack": v[1], "equal_to": list(real[0]), "equal": False,
+                                  "maxdiff": d}),
                       flush=True)
         times = {v: [] for v in variants}
         for _ in range(a.rounds):
@@ -117,9 +131,11 @@ def main():
         fl = 2.0 * N * H * W * OC * 9 * C
         for v in variants:
             med = statistics.median(times[v])
-            print(json.dumps({"case": case, "var": v, "ms_median": round(med, 4), "ms_min": round(min(times[v]), 4),
-                              "tflops": round(fl / med / 1e9, 1)}), flush=True)
+            print(json.dumps({"case": case, "var": v[0], "bpack": v[1], "ms_median": round(med, 4),
+                              "ms_min": round(min(times[v]), 4), "tflops": round(fl / med / 1e9, 1),
+                              "rounds_ms": [round(t, 4) for t in times[v]]}), flush=True)
     os.environ.pop("DV_KW3_VAR", None)
+    os.environ.pop("DV_KW3_BPACK", None)
 
 
 if __name__ == "__main__":
