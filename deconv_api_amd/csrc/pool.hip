@@ -170,6 +170,15 @@ __global__ void __launch_bounds__(256) maxpool_bwd_kernel(const uint16_t* __rest
   }
 }
 
+// a * b rounded to fp32 on its own, never contracted into an FMA with the add that follows: the window
+// average, and each window's share inv * gy of a gradient, is a value of its own, so avg + bias == 0 and
+// shares that cancel give 0 and not the rounding residue of the unrounded product (+-2^-25 for
+// 36 * (1.f / 9) - 4), which the ReLU and every emask downstream would read as a sign.
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
 __device__ __forceinline__ int win_count(int o, int s, int pad, int k, int L) {
   const int lo = max(0, o * s - pad), hi = min(L - 1, o * s - pad + k - 1);
   return hi - lo + 1;
@@ -209,7 +218,7 @@ __global__ void __launch_bounds__(256) avgpool_fwd_kernel(const uint16_t* __rest
     const float inv = 1.f / (float)(win_count(oh, g.s, g.pad, k, g.H) * win_count(ow, g.s, g.pad, k, g.W));
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      acc[e] = acc[e] * inv + (g.bias ? g.bias[ch * 8 + e] : 0.f);
+      acc[e] = mul_rn(acc[e], inv) + (g.bias ? g.bias[ch * 8 + e] : 0.f);
       if (g.relu) acc[e] = fmaxf(acc[e], 0.f);
     }
     uint4 o;
@@ -237,8 +246,9 @@ __global__ void __launch_bounds__(256) avgpool_bwd_kernel(const uint16_t* __rest
     float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (KC == 3 && g.s == 1 && !g.generic) {
       // 3x3 / stride 1 (the InceptionV3 pool branches): the windows containing (h, w) are
-      // oh = h + pad - 2 .. h + pad; all 9 loads issue (clamped) before the first use, summed in the
-      // generic loop's ascending (oh, ow) order with the same per-window divisor: bit-identical
+      // oh = h + pad - 2 .. h + pad; all 9 loads issue (clamped) before the first use, summed as the
+      // generic loop does (the rounded shares of one window row in ascending ow, then the rows in
+      // ascending oh: three short chains instead of one of nine) with the same divisors: bit-identical
       uint4 v[3][3];
       bool ok[3][3];
 #pragma unroll
@@ -254,7 +264,8 @@ __global__ void __launch_bounds__(256) avgpool_bwd_kernel(const uint16_t* __rest
         }
       }
 #pragma unroll
-      for (int a = 0; a < 3; ++a)
+      for (int a = 0; a < 3; ++a) {
+        float row[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
         for (int b = 0; b < 3; ++b) {
           if (!ok[a][b]) continue;
@@ -262,14 +273,18 @@ __global__ void __launch_bounds__(256) avgpool_bwd_kernel(const uint16_t* __rest
           const float inv = 1.f / (float)(win_count(oh, 1, g.pad, 3, g.H) * win_count(ow, 1, g.pad, 3, g.W));
           const uint32_t w4[4] = {v[a][b].x, v[a][b].y, v[a][b].z, v[a][b].w};
 #pragma unroll
-          for (int e = 0; e < 8; ++e) acc[e] += inv * to_f<DT>((w4[e >> 1] >> (16 * (e & 1))) & 0xFFFFu);
+          for (int e = 0; e < 8; ++e) row[e] += mul_rn(inv, to_f<DT>((w4[e >> 1] >> (16 * (e & 1))) & 0xFFFFu));
         }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[e] += row[e];
+      }
     } else {
     const int oh_lo = max(0, (h + g.pad - k + g.s) / g.s), oh_hi = min(g.OH - 1, (h + g.pad) / g.s);
     const int ow_lo = max(0, (w + g.pad - k + g.s) / g.s), ow_hi = min(g.OW - 1, (w + g.pad) / g.s);
     for (int oh = oh_lo; oh <= oh_hi; ++oh) {
       const int kh = h + g.pad - oh * g.s;
       if (kh < 0 || kh >= k) continue;
+      float row[8] = {0, 0, 0, 0, 0, 0, 0, 0};
       for (int ow = ow_lo; ow <= ow_hi; ++ow) {
         const int kw = w + g.pad - ow * g.s;
         if (kw < 0 || kw >= k) continue;
@@ -277,8 +292,10 @@ __global__ void __launch_bounds__(256) avgpool_bwd_kernel(const uint16_t* __rest
         const uint4 v = *reinterpret_cast<const uint4*>(gy + ((n * g.OH + oh) * g.OW + ow) * g.y_ld + ch * 8);
         const uint32_t w4[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-        for (int e = 0; e < 8; ++e) acc[e] += inv * to_f<DT>((w4[e >> 1] >> (16 * (e & 1))) & 0xFFFFu);
+        for (int e = 0; e < 8; ++e) row[e] += mul_rn(inv, to_f<DT>((w4[e >> 1] >> (16 * (e & 1))) & 0xFFFFu));
       }
+#pragma unroll
+      for (int e = 0; e < 8; ++e) acc[e] += row[e];
     }
     }
     if (g.acc) {  // accumulate into the existing gradient (one pass instead of pool + add)
