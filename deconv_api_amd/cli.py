@@ -19,13 +19,16 @@ from typing import List
 import numpy as np
 
 
-def _read(paths: List[str]) -> List[np.ndarray]:
-    from .codec import decode_image
+def _read(paths: List[str], coeffs: bool = False) -> list:
+    """Decoded images; with ``coeffs`` a baseline JPEG stays a JpegCoeffs for the GPU decode path."""
+    from .codec import decode_image, parse_jpeg_coeffs
 
     out = []
     for p in paths:
         with open(p, "rb") as f:
-            out.append(decode_image(f.read()))
+            data = f.read()
+        img = parse_jpeg_coeffs(data) if coeffs else None
+        out.append(decode_image(data) if img is None else img)
     return out
 
 
@@ -37,11 +40,10 @@ def cmd_deconv(a, cfg) -> int:
     from .codec import encode_jpeg
     from .serve.service import DeconvService
 
-    imgs = _read(a.images)
     svc = DeconvService(cfg)
     try:
         svc.engine._check_layer(a.layer)  # an unknown layer fails before any compute
-        mos = svc.run_batch(a.layer, imgs)
+        mos = svc.run_batch(a.layer, _read(a.images, svc.gpu_decode))
     finally:
         svc.close()
     os.makedirs(a.out_dir, exist_ok=True)
@@ -98,6 +100,8 @@ def main(argv=None) -> int:
     d.add_argument("--layer", default="block5_conv3")
     d.add_argument("--mode", default=None, help="all | max (DV_MODE)")
     d.add_argument("--out-dir", default=".")
+    d.add_argument("--gpu-decode", action="store_true", default=None,
+                   help="baseline JPEGs: entropy-decode on the host, the rest on the GPU (DV_GPU_JPEG_DECODE)")
     r = sub.add_parser("dream", help="DeepDream of each image")
     r.add_argument("images", nargs="+")
     r.add_argument("--model", default="inception_v3", choices=["inception_v3", "resnet50"])
@@ -110,7 +114,8 @@ def main(argv=None) -> int:
     from .config import Config
 
     over = {k: v for k, v in (("device", a.device), ("dtype", a.dtype), ("weights", a.weights),
-                              ("mode", getattr(a, "mode", None))) if v is not None}
+                              ("mode", getattr(a, "mode", None)),
+                              ("gpu_jpeg_decode", getattr(a, "gpu_decode", None))) if v is not None}
     cfg = Config.from_env(**over)
     from .codec import ImageDecodeError
     from .engine.deconvnet import UnknownLayerError

@@ -18,6 +18,8 @@ import base64
 import binascii
 import io
 import os
+from dataclasses import dataclass
+from typing import Optional
 from urllib.parse import quote
 
 import numpy as np
@@ -75,21 +77,79 @@ def decode_image(data: bytes) -> np.ndarray:
     return np.ascontiguousarray(arr)
 
 
-def read_data_url(uri: str) -> np.ndarray:
+@dataclass
+class JpegCoeffs:
+    """A baseline JPEG after the host's share of the GPU decode path (csrc/jpeg_dec.cpp): header +
+    quantized DCT coefficients. The device turns it into the RGB bytes PIL would have decoded
+    (csrc/jpeg_dec_gpu.hip, ops/jpeg_dec.py); until then it stands in for the HxWx3 array."""
+    H: int
+    W: int
+    ncomp: int          # 1 (greyscale) or 3 (YCbCr)
+    kind: int           # ops/jpeg_dec.py: K444, K422, K420, KGREY
+    qt: np.ndarray      # uint16 [ncomp, 64]: each component's quantizer, natural (row-major) order
+    coef: np.ndarray    # int16 [blocks * 64]: component-major, MCU-padded, blocks column-major
+
+    @property
+    def shape(self):
+        return (self.H, self.W, 3)
+
+    @property
+    def size(self) -> int:
+        return self.H * self.W * 3
+
+
+def _coeffs_from_native(res) -> "JpegCoeffs":
+    (H, W, ncomp, kind, qt), coef = res
+    return JpegCoeffs(int(H), int(W), int(ncomp), int(kind), np.frombuffer(qt, dtype="<u2").reshape(ncomp, 64),
+                      coef.numpy())
+
+
+def parse_jpeg_coeffs(data: bytes) -> Optional[JpegCoeffs]:
+    """The native entropy decode of a baseline JPEG (GIL released), or None when the file is outside the
+    accepted subset (progressive, CMYK, rotated by Exif, damaged, over DV_MAX_PIXELS, not a JPEG ...):
+    the caller then decodes with PIL, so every response stays what it was. Needs the extension."""
+    from ..ops import native
+
+    res = native.lib().jpeg_parse_coeffs(bytes(data), MAX_PIXELS)
+    return None if res is None else _coeffs_from_native(res)
+
+
+def read_data_url(uri: str, coeffs: bool = False):
     """The reference's ``readb64``. With the extension built, the payload is split out and
     base64-decoded natively with the GIL released (csrc/jpeg_enc.cpp:data_url_b64decode, CPython's
     non-strict semantics and messages): the Python decode held the GIL ~0.24 ms per 60 KB request,
-    serialized across the codec pool's threads."""
+    serialized across the codec pool's threads.
+
+    ``coeffs=True`` (the GPU JPEG decode path, Config.gpu_jpeg_decode): a ``JpegCoeffs`` when the payload
+    is a JPEG the native parser accepts, else the decoded array as always."""
     lib = _native()
     if lib is not None and isinstance(uri, str) and uri.isascii():
         if "," not in uri:
             split_data_url(uri)  # raises the data-URL error
         try:
-            data = lib.data_url_b64decode(uri)
+            if coeffs:
+                data, parsed = lib.data_url_parse_coeffs(uri, MAX_PIXELS)
+                if parsed is not None:
+                    return _coeffs_from_native(parsed)
+            else:
+                data = lib.data_url_b64decode(uri)
         except ValueError as e:
             raise ImageDecodeError(f"bad base64 payload: {e}") from e
         return decode_image(data)
-    return decode_image(b64decode_lenient(split_data_url(uri)))
+    data = b64decode_lenient(split_data_url(uri))
+    if coeffs and lib is not None:
+        parsed = parse_jpeg_coeffs(data)
+        if parsed is not None:
+            return parsed
+    return decode_image(data)
+
+
+def decode_path(uri: str, img, gpu_decode: bool) -> str:
+    """The dv_decode_path_total label of one decoded request."""
+    if isinstance(img, JpegCoeffs):
+        return "gpu"
+    jpeg = uri[:64].split(",", 1)[-1].startswith("/9j/")  # base64 of the SOI marker FF D8 FF
+    return "pil_fallback" if gpu_decode and jpeg else "pil"
 
 
 def _native():

@@ -52,6 +52,11 @@ class Config:
     native_codec: bool = True             # native encoder for responses (PIL fallback when False/unbuilt)
     gpu_jpeg: bool = True                 # GPU: responses JPEG-encoded on the device (csrc/jpeg_gpu.hip);
                                           #   the host only base64s the scans
+    gpu_jpeg_decode: bool = False         # baseline JPEG requests: the host only entropy-decodes (csrc/jpeg_dec.cpp),
+                                          #   IDCT + upsampling + colour run on the device (csrc/jpeg_dec_gpu.hip),
+                                          #   bit-identical to PIL; anything else still goes through PIL. Takes
+                                          #   effect only on a CUDA device with the staging ring: not on the CPU
+                                          #   engine, not in the DV_FRONTENDS=0 multi-rank (sharded) runner
     cors_origins: Tuple[str, ...] = ("*",)  # app/main.py:22-32
     host: str = "0.0.0.0"
     port: int = 80                        # Dockerfile:10,15

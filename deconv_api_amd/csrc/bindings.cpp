@@ -5,6 +5,7 @@
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 
+#include "jpeg_dec.h"
 #include "jpeg_enc.h"
 #include "kernels.h"
 
@@ -1174,6 +1175,106 @@ py::bytes jpeg_encode(Tensor img, int64_t quality) {
   return py::bytes(s);
 }
 
+// ---- GPU JPEG decode: host entropy decode (jpeg_dec.cpp) ----
+// None when the file is outside the accepted subset (the caller decodes it with PIL), else
+// ((H, W, components, kind, quantizers as little-endian uint16 bytes [components][64], natural order),
+//  int16 CPU tensor of the coefficients in jpeg_dec.h's layout). Call with the GIL released.
+static bool parse_coeffs_nogil(const uint8_t* p, size_t n, long long max_pixels, dvjpeg::DecHeader& h, Tensor& coef) {
+  if (dvjpeg::jpeg_dec_probe(p, n, max_pixels, h) != dvjpeg::DEC_OK) return false;
+  // empty + memset, not at::zeros: ATen fills large tensors on its intra-op thread pool, and this runs on
+  // every codec thread of every front-end process at once (the pools' spinning workers starved the box)
+  coef = at::empty({(int64_t)dvjpeg::dec_total_blocks(h) * 64}, at::TensorOptions().dtype(at::kShort));
+  std::memset(coef.data_ptr(), 0, (size_t)coef.numel() * sizeof(int16_t));
+  return dvjpeg::jpeg_dec_decode(p, n, h, coef.data_ptr<int16_t>()) == dvjpeg::DEC_OK;
+}
+static py::object coeffs_result(const dvjpeg::DecHeader& h, const Tensor& coef) {
+  std::string q((size_t)h.ncomp * 128, '\0');
+  for (int c = 0; c < h.ncomp; ++c)
+    for (int k = 0; k < 64; ++k) {
+      q[(size_t)c * 128 + 2 * k] = (char)(h.qt[c][k] & 0xFF);
+      q[(size_t)c * 128 + 2 * k + 1] = (char)(h.qt[c][k] >> 8);
+    }
+  return py::make_tuple(py::make_tuple(h.H, h.W, h.ncomp, h.kind, py::bytes(q)), coef);
+}
+
+py::object jpeg_parse_coeffs(py::bytes data, int64_t max_pixels) {
+  char* p = nullptr;
+  Py_ssize_t n = 0;
+  if (PyBytes_AsStringAndSize(data.ptr(), &p, &n) != 0) throw py::error_already_set();
+  dvjpeg::DecHeader h;
+  Tensor coef;
+  bool ok;
+  {
+    py::gil_scoped_release nogil;
+    ok = parse_coeffs_nogil(reinterpret_cast<const uint8_t*>(p), (size_t)n, max_pixels, h, coef);
+  }
+  return ok ? coeffs_result(h, coef) : py::none();
+}
+
+// data URL -> (None, parsed) when the payload is an accepted JPEG, else (payload bytes, None): the base64
+// step of data_url_b64decode and the parse in one GIL-free call, without a Python bytes object in between
+py::tuple data_url_parse_coeffs(py::str uri, int64_t max_pixels) {
+  PyObject* o = uri.ptr();
+  if (!PyUnicode_IS_ASCII(o)) throw py::type_error("string argument should contain only ASCII characters");
+  Py_ssize_t n = 0;
+  const char* p = PyUnicode_AsUTF8AndSize(o, &n);
+  if (p == nullptr) throw py::error_already_set();
+  std::string out, err;
+  dvjpeg::DecHeader h;
+  Tensor coef;
+  bool ok, parsed = false;
+  {
+    py::gil_scoped_release nogil;
+    ok = dvjpeg::data_url_b64decode(p, (size_t)n, out, err);
+    if (ok) parsed = parse_coeffs_nogil(reinterpret_cast<const uint8_t*>(out.data()), out.size(), max_pixels, h, coef);
+  }
+  if (!ok) throw py::value_error(err);
+  if (parsed) return py::make_tuple(py::none(), coeffs_result(h, coef));
+  return py::make_tuple(py::bytes(out), py::none());
+}
+
+// GPU half (jpeg_dec_gpu.hip). blob: device uint8, holding the coefficients and quantizers the table points
+// at and room for the planes and the RGB output; table / table_host: the same int32 [B, 12] rows on the device
+// and on the host. Every row is checked against the blob here, on the host copy: extents, alignment of what
+// the kernels load as vectors, and the work-item prefixes.
+void jpeg_dec_batch(Tensor blob, Tensor table, Tensor table_host) {
+  check_cuda(blob, "blob");
+  check_cuda(table, "table");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(blob.device());
+  TORCH_CHECK(blob.scalar_type() == at::kByte && blob.is_contiguous() && blob.dim() == 1 &&
+                  reinterpret_cast<uintptr_t>(blob.data_ptr()) % 16 == 0,
+              "jpeg_dec_batch: blob u8 [bytes], 16-byte aligned");
+  const int64_t nb = blob.numel();
+  TORCH_CHECK(nb > 0 && nb <= 0x7FFFFFFFLL, "jpeg_dec_batch: blob of 1 .. 2^31 - 1 bytes (32-bit offsets)");
+  TORCH_CHECK(!table_host.is_cuda() && table_host.scalar_type() == at::kInt && table_host.is_contiguous() &&
+                  table_host.dim() == 2 && table_host.size(1) == 12 && table_host.size(0) >= 1,
+              "jpeg_dec_batch: table_host int32 CPU [B, 12]");
+  TORCH_CHECK(table.scalar_type() == at::kInt && table.is_contiguous() && table.sizes() == table_host.sizes() &&
+                  table.device() == blob.device(),
+              "jpeg_dec_batch: table int32 [B, 12] on the blob's device");
+  const int B = (int)table_host.size(0);
+  const int32_t* t = table_host.data_ptr<int32_t>();
+  int64_t blocks = 0, items = 0;
+  for (int b = 0; b < B; ++b, t += 12) {
+    const int64_t coef = t[0], rgb = t[1], H = t[2], W = t[3], kind = t[4], qt = t[5], plane = t[6];
+    TORCH_CHECK(H >= 1 && W >= 1 && H <= 65535 && W <= 65535 && kind >= 0 && kind <= 3, "jpeg_dec_batch: row ", b, ": size / kind");
+    const int64_t hs = (kind == 1 || kind == 2) ? 2 : 1, vs = kind == 2 ? 2 : 1;
+    const int64_t nC = ((W + 8 * hs - 1) / (8 * hs)) * ((H + 8 * vs - 1) / (8 * vs));
+    const int64_t nblk = nC * hs * vs + (kind == 3 ? 0 : 2 * nC);
+    TORCH_CHECK(coef >= 0 && coef % 16 == 0 && coef + nblk * 128 <= nb, "jpeg_dec_batch: row ", b, ": coefficients outside the blob");
+    TORCH_CHECK(qt >= 0 && qt % 16 == 0 && qt + 384 <= nb, "jpeg_dec_batch: row ", b, ": quantizers outside the blob");
+    TORCH_CHECK(plane >= 0 && plane % 16 == 0 && plane + nblk * 64 <= nb, "jpeg_dec_batch: row ", b, ": planes outside the blob");
+    TORCH_CHECK(rgb >= 0 && rgb + H * W * 3 <= nb, "jpeg_dec_batch: row ", b, ": RGB outside the blob");
+    TORCH_CHECK(t[7] == blocks && t[8] == items, "jpeg_dec_batch: row ", b, ": work-item prefix");
+    blocks += nblk;
+    items += H * ((W + 3) / 4);
+    TORCH_CHECK(blocks <= 0x7FFFFFFFLL - 64 && items <= 0x7FFFFFFFLL - 512, "jpeg_dec_batch: too many work items");
+  }
+  check_rc(dv::jpeg_dec_launch(blob.data_ptr<uint8_t>(), nb, table.data_ptr<int32_t>(), B, (int)blocks, (int)items,
+                               cur_stream()),
+           "jpeg_dec_batch");
+}
+
 // bench.py --emulate-rccl-world: a paced copy occupying `channels` CUs for bytes / gbs (an all-gather's
 // receive side at a given link bandwidth; misc.hip:paced_copy_kernel)
 void paced_copy(Tensor src, Tensor dst, int64_t channels, double gbs) {
@@ -1567,6 +1668,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("jpeg_gpu_max_width", &dv::jpeg_gpu_max_width, "widest image the GPU encoder takes");
   m.def("jpeg_gpu_data_urls", &jpeg_gpu_data_urls, "GPU scans -> data URLs (host base64, GIL released)");
   m.def("jpeg_encode", &jpeg_encode, "native baseline JPEG encode (GIL released)");
+  m.def("jpeg_parse_coeffs", &jpeg_parse_coeffs, "baseline JPEG bytes -> None | (header, int16 coefficients) (GIL released)");
+  m.def("data_url_parse_coeffs", &data_url_parse_coeffs, "data URL -> (payload | None, None | parsed coefficients)");
+  m.def("jpeg_dec_batch", &jpeg_dec_batch, "GPU JPEG decode of a batch: coefficients -> RGB, two launches");
   m.def("channel_sum", &channel_sum);
   m.def("topk_pos", &topk_pos);
   m.def("seed_deconv3x3", &seed_deconv3x3);

@@ -272,6 +272,12 @@ long long jpeg_gpu_out_cap(int H, int W);
 int jpeg_gpu_max_width();
 int jpeg_gpu_launch(const uint8_t* rgb, int B, int H, int W, const void* tables, void* ws, uint8_t* packed,
                     long long* off, hipStream_t s);
+// GPU JPEG decode of a batch (jpeg_dec_gpu.hip): dequantize + IDCT into planes, then chroma upsampling +
+// colour into packed RGB, two launches. `table`: device int32 [B][12] rows {coefficient offset, RGB offset,
+// H, W, kind, quantizer offset, plane offset, first block, first 4-pixel item, 0, 0, 0}, byte offsets into
+// `blob` (validated by bindings.cpp:jpeg_dec_batch); total_blocks / total_items: the sums behind the prefixes
+int jpeg_dec_launch(uint8_t* blob, long long blob_bytes, const int* table, int B, int total_blocks, int total_items,
+                    hipStream_t s);
 // row softmax (fp32 [M][N])
 int softmax_rows_launch(const float* x, float* y, int M, int N, hipStream_t s);
 // bench.py --emulate-rccl-world: `channels` workgroups copy `bytes` (src repeated) paced to `gbs` GB/s (misc.hip)

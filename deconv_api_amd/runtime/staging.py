@@ -23,7 +23,8 @@ from typing import List, Optional
 import numpy as np
 import torch
 
-from ..ops import native
+from ..codec.image import JpegCoeffs
+from ..ops import jpeg_dec, native
 from ..ops.misc import resize_mode
 from ..utils import metrics as M
 
@@ -59,19 +60,46 @@ class GpuScans:
         return self.off.numel() - 1
 
 
-def resize_batch(images: List[np.ndarray], out: torch.Tensor) -> torch.Tensor:
-    """Unstaged one-shot form (tools / tests): pack, upload synchronously, one batched resize."""
-    offs, end = [], 0
-    for im in images:
-        offs.append(end)
+def _layout(images, S_h: int, S_w: int):
+    """Byte layout of a batch in a slot. Pixel images are packed back to back from 0 as always; the
+    coefficients and quantizers of JpegCoeffs images follow them (all of that is written by the host and
+    uploaded: [0, upload_end)); behind it, device-only, come their planes and decoded RGB, where the
+    resize table points for those images. -> (resize rows, pixel (index, offset) pairs, coefficient
+    indices, decode table or None, upload_end, end)."""
+    rows, pix, jidx, end = [None] * len(images), [], [], 0
+    for b, im in enumerate(images):
+        if isinstance(im, JpegCoeffs):
+            jidx.append(b)
+            continue
+        assert im.dtype == np.uint8 and im.ndim == 3 and im.shape[2] == 3
+        pix.append((b, end))
+        rows[b] = (end, im.shape[0], im.shape[1], resize_mode(im.shape[0], im.shape[1], S_h, S_w))
         end = _round_up(end + im.size, 16)
-    blob = np.zeros(max(end, 16), np.uint8)
+    if not jidx:
+        return rows, pix, jidx, None, end, end
+    jtab, upload_end, end = jpeg_dec.plan_batch([images[b] for b in jidx], end)
+    for r, b in zip(jtab, jidx):
+        rows[b] = (int(r[1]), int(r[2]), int(r[3]), resize_mode(int(r[2]), int(r[3]), S_h, S_w))
+    return rows, pix, jidx, jtab, upload_end, end
+
+
+def resize_batch(images: List[np.ndarray], out: torch.Tensor) -> torch.Tensor:
+    """Unstaged one-shot form (tools / tests): pack, upload synchronously, one batched resize (after the
+    GPU JPEG decode of the JpegCoeffs images among ``images``, if any)."""
+    rows, pix, jidx, jtab, upload_end, end = _layout(images, out.shape[1], out.shape[2])
+    blob = np.zeros(max(upload_end, 16), np.uint8)
     tab = np.zeros((len(images), 4), np.int64)
-    for b, (im, o) in enumerate(zip(images, offs)):
-        blob[o:o + im.size] = np.ascontiguousarray(im).reshape(-1)
-        tab[b] = (o, im.shape[0], im.shape[1], resize_mode(im.shape[0], im.shape[1], out.shape[1], out.shape[2]))
-    native.lib().resize_batch(torch.from_numpy(blob).to(out.device), torch.from_numpy(tab).to(out.device),
-                              out[: len(images)], end)
+    for b, o in pix:
+        blob[o:o + images[b].size] = np.ascontiguousarray(images[b]).reshape(-1)
+    tab[:] = rows
+    dev = torch.empty(max(end, 16), dtype=torch.uint8, device=out.device)
+    if jidx:
+        jpeg_dec.fill_batch(blob, jtab, [images[b] for b in jidx])
+    dev[: blob.size].copy_(torch.from_numpy(blob))
+    if jidx:
+        jt = torch.from_numpy(jtab)
+        native.lib().jpeg_dec_batch(dev, jt.to(out.device), jt)
+    native.lib().resize_batch(dev, torch.from_numpy(tab).to(out.device), out[: len(images)], end)
     return out
 
 
@@ -92,6 +120,9 @@ class StagingRing:
         self.dev: List[Optional[torch.Tensor]] = [None] * slots
         self.tab_host = torch.empty(slots, max_images, 4, dtype=torch.int64, pin_memory=True)
         self.tab_dev = torch.empty(slots, max_images, 4, dtype=torch.int64, device=device)
+        # GPU JPEG decode (JpegCoeffs images): one decode-table row per such image (ops/jpeg_dec.py)
+        self.jtab_host = torch.empty(slots, max_images, jpeg_dec.TAB_FIELDS, dtype=torch.int32, pin_memory=True)
+        self.jtab_dev = torch.empty(slots, max_images, jpeg_dec.TAB_FIELDS, dtype=torch.int32, device=device)
         self.out_dev: List[Optional[torch.Tensor]] = [None] * slots
         self.busy: List[Optional[Staged]] = [None] * slots  # the batch last staged in each slot
         # per slot: recorded on the compute stream right after the slot's resize launch, the last
@@ -102,13 +133,16 @@ class StagingRing:
         for i in range(slots):
             self._ensure(i, slot_bytes)
 
-    def _ensure(self, i: int, nbytes: int) -> None:
-        if self._bytes[i] >= nbytes:
-            return
-        cap = 1 << max(20, (nbytes - 1).bit_length())
-        self.host[i] = torch.empty(cap, dtype=torch.uint8, pin_memory=True)
-        self.dev[i] = torch.empty(cap, dtype=torch.uint8, device=self.device)
-        self._bytes[i] = cap
+    def _ensure(self, i: int, nbytes: int, dev_bytes: int = 0) -> None:
+        """Slot i holds ``nbytes`` on the host and max(nbytes, dev_bytes) on the device (the device-only
+        region of a batch with JpegCoeffs images lies behind the uploaded part)."""
+        if self._bytes[i] < nbytes:
+            cap = 1 << max(20, (nbytes - 1).bit_length())
+            self.host[i] = torch.empty(cap, dtype=torch.uint8, pin_memory=True)
+            self._bytes[i] = cap
+        need = max(self._bytes[i], dev_bytes)
+        if self.dev[i] is None or self.dev[i].numel() < need:
+            self.dev[i] = torch.empty(1 << max(20, (need - 1).bit_length()), dtype=torch.uint8, device=self.device)
 
     def _acquire(self) -> int:
         with self._lock:
@@ -121,23 +155,26 @@ class StagingRing:
 
     # ------------------------------------------------------------------ upload + resize
     def stage(self, images: List[np.ndarray], out: torch.Tensor) -> Staged:
-        """Pack ``images`` (uint8 HxWx3, any sizes) into a slot, upload, and resize into ``out``
-        ([n, S, S, Cpad] bf16 preprocessed, or [n, S, S, 3] uint8) on the compute stream."""
+        """Pack ``images`` (uint8 HxWx3 of any sizes, or JpegCoeffs) into a slot, upload, and resize into
+        ``out`` ([n, S, S, Cpad] bf16 preprocessed, or [n, S, S, 3] uint8) on the compute stream.
+        JpegCoeffs images upload their coefficients instead of pixels and are decoded into the slot's
+        device-only region by one batched launch pair ahead of the resize (csrc/jpeg_dec_gpu.hip)."""
         n = len(images)
         assert 0 < n <= self.max_images and out.shape[0] >= n
         S_h, S_w = out.shape[1], out.shape[2]
         i = self._acquire()
-        offs, end = [], 0
-        for im in images:
-            assert im.dtype == np.uint8 and im.ndim == 3 and im.shape[2] == 3
-            offs.append(end)
-            end = _round_up(end + im.size, 16)
-        self._ensure(i, end)
+        rows, pix, jidx, jtab, upload_end, total = _layout(images, S_h, S_w)
+        end = upload_end  # what the host writes and the H2D copy moves
+        self._ensure(i, end, total)
         hv = self.host[i].numpy()
         tab = self.tab_host[i].numpy()
-        for b, (im, o) in enumerate(zip(images, offs)):
-            hv[o:o + im.size] = np.ascontiguousarray(im).reshape(-1)
-            tab[b] = (o, im.shape[0], im.shape[1], resize_mode(im.shape[0], im.shape[1], S_h, S_w))
+        for b, o in pix:
+            hv[o:o + images[b].size] = np.ascontiguousarray(images[b]).reshape(-1)
+        tab[:n] = rows
+        nj = len(jidx)
+        if nj:
+            jpeg_dec.fill_batch(hv, jtab, [images[b] for b in jidx])
+            self.jtab_host[i, :nj].numpy()[:] = jtab
         st = Staged(i, n, torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True),
                     torch.cuda.Event(enable_timing=True))
         cur = torch.cuda.current_stream(self.device)
@@ -149,10 +186,14 @@ class StagingRing:
             st.ev_h2d0.record()
             self.dev[i][:end].copy_(self.host[i][:end], non_blocking=True)
             self.tab_dev[i, :n].copy_(self.tab_host[i, :n], non_blocking=True)
+            if nj:
+                self.jtab_dev[i, :nj].copy_(self.jtab_host[i, :nj], non_blocking=True)
             st.ev_h2d1.record()
         cur.wait_event(st.ev_h2d1)
         st.ev_comp0.record(cur)
-        native.lib().resize_batch(self.dev[i], self.tab_dev[i, :n], out[:n], end)
+        if nj:  # coefficients -> RGB in the device-only region, where the resize table points
+            native.lib().jpeg_dec_batch(self.dev[i], self.jtab_dev[i, :nj], self.jtab_host[i, :nj])
+        native.lib().resize_batch(self.dev[i], self.tab_dev[i, :n], out[:n], total)
         ev = torch.cuda.Event()
         ev.record(cur)
         self.resized[i] = ev

@@ -20,7 +20,8 @@ import os
 import socket
 import time
 
-from ..codec import CodecPool, read_data_url
+from ..codec import CodecPool, JpegCoeffs, read_data_url
+from ..codec.image import decode_path
 from ..config import Config
 from ..engine.deconvnet import UnknownLayerError
 from ..utils import metrics as M
@@ -76,6 +77,9 @@ class RemoteService(_Remote):
         info = json.loads(data)
         self.layers = info["layers"]
         self._names = set(info["names"])  # every engine name: the owner answers e.g. input_1 itself
+        # GPU JPEG decode is the OWNER's switch: a front end sends coefficient frames only to an owner that
+        # said it takes them
+        self.gpu_decode = bool(info.get("gpu_jpeg_decode", False))
         self.codec = CodecPool(cfg.codec_workers)
 
     def layer_names(self):
@@ -87,8 +91,12 @@ class RemoteService(_Remote):
 
     def _decode_send(self, uri: str, layer: str, cb) -> None:
         t0 = time.perf_counter()
-        img = read_data_url(uri)  # ImageDecodeError -> 400 in the app
+        img = read_data_url(uri, self.gpu_decode)  # ImageDecodeError -> 400 in the app
+        M.DECODE_PATH.inc(path=decode_path(uri, img, self.gpu_decode))
         # the owner records it (its /metrics then cover every front end of the rank)
+        if isinstance(img, JpegCoeffs):
+            self.client.send_jpeg(cb, layer, img, decode_s=time.perf_counter() - t0)
+            return
         self.client.send(ingest.DECONV, cb, layer, img.shape[0], img.shape[1], img,
                          decode_s=time.perf_counter() - t0)
 

@@ -21,7 +21,10 @@ Wire format (little endian), both directions over one SOCK_STREAM Unix socket pe
   request   <I rid, B kind, B pad, H layer_len, I h, I w, Q nbytes, I decode_us> + layer utf-8 + payload
   response  <I rid, H status, Q nbytes> + payload
 kinds: DECONV (payload = h*w*3 uint8 RGB pixels), STATUS / METRICS / LAYERS (no payload; JSON or
-text back), DREAM (payload = JSON header line + the data URL). status: HTTP-like (200, 400, 503,
+text back), DREAM (payload = JSON header line + the data URL), DECONV_JPEG (GPU JPEG decode, sent only to
+an owner whose LAYERS reply says ``gpu_jpeg_decode``; payload = <B components, B kind, H 0> + the
+components' quantizers (uint16 [components][64]) + the int16 coefficients of codec.JpegCoeffs, whose
+count follows from h, w and kind). status: HTTP-like (200, 400, 503,
 500); non-200 payloads are the error message. ``decode_us``: the front end's base64 + PIL decode time,
 recorded by the owner, whose /metrics therefore cover every front end of the rank.
 """
@@ -38,7 +41,8 @@ from typing import Callable, Dict, Optional
 
 import numpy as np
 
-from ..codec.image import MAX_PIXELS
+from ..codec.image import MAX_PIXELS, JpegCoeffs
+from ..ops import jpeg_dec
 from ..utils import metrics as M
 from ..utils.logging import get_logger
 
@@ -46,7 +50,8 @@ log = get_logger("deconv_api_amd.ingest")
 
 REQ = struct.Struct("<IBBHIIQI")
 RESP = struct.Struct("<IHQ")
-DECONV, STATUS, METRICS, LAYERS, DREAM = 1, 2, 3, 4, 5
+DECONV, STATUS, METRICS, LAYERS, DREAM, DECONV_JPEG = 1, 2, 3, 4, 5, 6
+JPEG_HEAD = struct.Struct("<BBH")
 SOCK_BUF = 8 << 20
 MAX_DREAM_BODY = 256 << 20  # JSON header + data URL of one /deepdream request
 
@@ -156,6 +161,27 @@ class IngestServer:
                     self.requests += 1
                     M.HOST_STAGE.observe(dec_us * 1e-6, stage="decode")
                     self._deconv(rid, layer, img, reply)
+                elif kind == DECONV_JPEG:
+                    # sizes are checked against the header BEFORE anything is received, as for DECONV
+                    ncomp, jkind, _ = JPEG_HEAD.unpack(_recv_exact(c, JPEG_HEAD.size)) if nbytes >= JPEG_HEAD.size else (0, 0, 0)
+                    ok = (getattr(self.svc, "gpu_decode", False) and 1 <= h <= 65535 and 1 <= w <= 65535
+                          and h * w <= MAX_PIXELS and jkind in (0, 1, 2, 3) and ncomp == (1 if jkind == 3 else 3))
+                    ncoef = 64 * jpeg_dec.total_blocks(h, w, jkind) if ok else 0
+                    if not ok or nbytes != JPEG_HEAD.size + ncomp * 128 + ncoef * 2:
+                        reply(rid, 400, b"coefficient payload does not match its header, exceeds DV_MAX_PIXELS, "
+                                        b"or GPU JPEG decode is off")
+                        return
+                    # the VALUES are taken as sent: the exactness bound of the device IDCT (and q != 0) is
+                    # enforced by the sender's parser only. Front ends are this rank's own processes, and the
+                    # kernels index by the header alone (bindings.cpp checks every extent), so bad values
+                    # could cost pixels, never memory
+                    qt = np.empty((ncomp, 64), np.uint16)
+                    coef = np.empty(ncoef, np.int16)
+                    _recv_into(c, memoryview(qt).cast("B"))
+                    _recv_into(c, memoryview(coef).cast("B"))
+                    self.requests += 1
+                    M.HOST_STAGE.observe(dec_us * 1e-6, stage="decode")
+                    self._deconv(rid, layer, JpegCoeffs(h, w, ncomp, jkind, qt, coef), reply)
                 elif kind == DREAM:
                     if nbytes > MAX_DREAM_BODY:
                         reply(rid, 413, b"dream request too large")
@@ -234,7 +260,10 @@ class IngestServer:
             if kind == METRICS:
                 return 200, M.REGISTRY.render().encode()
             if kind == LAYERS:
-                return 200, json.dumps({"layers": self.svc.layer_names(), "names": list(self.svc.engine.names)}).encode()
+                info = {"layers": self.svc.layer_names(), "names": list(self.svc.engine.names)}
+                if getattr(self.svc, "gpu_decode", False):  # only an owner that takes DECONV_JPEG frames says so:
+                    info["gpu_jpeg_decode"] = True          # with the switch off the reply is what it always was
+                return 200, json.dumps(info).encode()
         except Exception as e:  # noqa: BLE001
             return 500, repr(e).encode()
         return 400, b"unknown request kind"
@@ -285,15 +314,24 @@ class IngestClient:
 
     def send(self, kind: int, cb: Callable[[int, bytes], None], layer: str = "", h: int = 0, w: int = 0,
              payload=b"", decode_s: float = 0.0) -> None:
-        """Queue one request; ``cb(status, payload)`` runs on the reader thread."""
-        mv = memoryview(payload).cast("B") if not isinstance(payload, (bytes, bytearray)) else payload
+        """Queue one request; ``cb(status, payload)`` runs on the reader thread. ``payload``: one
+        buffer, or a tuple of buffers sent back to back."""
+        parts = payload if isinstance(payload, tuple) else (payload,)
+        mvs = [memoryview(x).cast("B") if not isinstance(x, (bytes, bytearray)) else x for x in parts]
         lb = layer.encode()
         rid = self._next(cb)
-        head = REQ.pack(rid, kind, 0, len(lb), h, w, len(mv), min(int(decode_s * 1e6), 0xFFFFFFFF))
+        head = REQ.pack(rid, kind, 0, len(lb), h, w, sum(len(mv) for mv in mvs), min(int(decode_s * 1e6), 0xFFFFFFFF))
         with self._send:
             self.sock.sendall(head + lb)
-            if len(mv):
-                self.sock.sendall(mv)
+            for mv in mvs:
+                if len(mv):
+                    self.sock.sendall(mv)
+
+    def send_jpeg(self, cb, layer: str, c: JpegCoeffs, decode_s: float = 0.0) -> None:
+        """One DECONV_JPEG request: the coefficients of ``c`` instead of its pixels."""
+        self.send(DECONV_JPEG, cb, layer, c.H, c.W,
+                  (JPEG_HEAD.pack(c.ncomp, c.kind, 0), np.ascontiguousarray(c.qt, dtype=np.uint16),
+                   np.ascontiguousarray(c.coef, dtype=np.int16)), decode_s=decode_s)
 
     def call(self, kind: int, layer: str = "", payload=b"", timeout: float = 30.0):
         """Blocking request (status / metrics / layers) -> (status, payload)."""

@@ -29,7 +29,7 @@ import torch
 
 from .. import ops
 from ..codec import CodecPool, encode_data_url, encode_data_urls, read_data_url
-from ..codec.image import gpu_data_urls, gpu_jpeg_fits
+from ..codec.image import JpegCoeffs, decode_path, gpu_data_urls, gpu_jpeg_fits
 from ..runtime.staging import GpuScans
 from ..config import Config
 from ..engine.deconvnet import DeconvNet, UnknownLayerError
@@ -55,7 +55,7 @@ class _Job:
     request of this process it completes an asyncio future on the request's loop, for a request
     from a front-end process (serve/ingest.py) it writes the response to that front-end's socket."""
     layer: str
-    image: np.ndarray
+    image: object  # np.ndarray HxWx3 uint8, or codec.JpegCoeffs (decoded on the device by the staging ring)
     deliver: Callable[[object, Optional[BaseException]], None]
     t_enq: float = field(default_factory=time.perf_counter)
     t_launch: float = 0.0
@@ -106,6 +106,8 @@ class DeconvService:
                 self.graphs = GraphedDeconv(engine, self.cfg.image_size, self.cfg.filters, self.cfg.mode)
         elif runner is not None and runner.graphs is not None:
             self.graphs = runner.graphs  # the runner replays its own per-(layer, shard) graphs
+        # GPU JPEG decode needs the staging ring (the decode launch sits between its upload and its resize)
+        self.gpu_decode = bool(self.cfg.gpu_jpeg_decode and self.ring is not None and ops.native.available())
         self.codec = CodecPool(self.cfg.codec_workers)
         from concurrent.futures import ThreadPoolExecutor
 
@@ -145,11 +147,13 @@ class DeconvService:
     def layer_names(self) -> List[str]:
         return [s.name for s in self.engine.specs[1:]]
 
-    def submit(self, layer: str, img: np.ndarray, deliver) -> _Job:
-        """Enqueue an already decoded HxWx3 uint8 image; ``deliver(value, exc)`` is called from a
-        service thread with the response string (or the error). Raises at once for an unknown
-        layer or a full queue."""
+    def submit(self, layer: str, img, deliver) -> _Job:
+        """Enqueue an already decoded HxWx3 uint8 image (or, with ``gpu_decode``, a JpegCoeffs);
+        ``deliver(value, exc)`` is called from a service thread with the response string (or the
+        error). Raises at once for an unknown layer or a full queue."""
         self.validate_layer(layer)
+        if isinstance(img, JpegCoeffs) and not self.gpu_decode:
+            raise ValueError("this service does not take JPEG coefficients (DV_GPU_JPEG_DECODE is off)")
         if self.q.qsize() >= self.cfg.max_queue:
             raise ServiceOverloaded("request queue is full")
         job = _Job(layer, img, deliver)
@@ -164,8 +168,9 @@ class DeconvService:
             raise ServiceOverloaded("request queue is full")
         loop = asyncio.get_running_loop()
         t0 = time.perf_counter()
-        img = await loop.run_in_executor(self.codec.ex, read_data_url, uri)
+        img = await loop.run_in_executor(self.codec.ex, read_data_url, uri, self.gpu_decode)
         M.HOST_STAGE.observe(time.perf_counter() - t0, stage="decode")
+        M.DECODE_PATH.inc(path=decode_path(uri, img, self.gpu_decode))
         fut = loop.create_future()
         job = self.submit(layer, img, lambda v, e: _deliver(loop, _set_exc if e is not None else _set_result,
                                                             fut, e if e is not None else v))
@@ -181,7 +186,7 @@ class DeconvService:
               "stalled": self.stalled, "queue_depth": self.q.qsize(),
               "batches": self.batches, "images": self.images, "last_error": self.last_error,
               "native": ops.native.available() if self.device.type == "cuda" else None,
-              "native_codec": self.native_codec,
+              "native_codec": self.native_codec, "gpu_jpeg_decode": self.gpu_decode,
               "graphs": [f"{l}:{b}" for l, b in self.graphs.captured] if self.graphs else None}
         if self.device.type == "cuda":
             st["gpu"] = torch.cuda.get_device_name(self.device)

@@ -150,6 +150,9 @@ BATCH_SIZE = REGISTRY.histogram("dv_batch_size", "images per engine batch",
 ENGINE_TIME = REGISTRY.histogram("dv_engine_seconds", "engine time per batch by stage")
 QUEUE_DEPTH = REGISTRY.gauge("dv_queue_depth", "pending requests in the batcher")
 IMAGES = REGISTRY.counter("dv_images_total", "images processed by the engine")
+DECODE_PATH = REGISTRY.counter("dv_decode_path_total",
+                               "requests by image decode path: gpu (native parse + device decode), pil (switch off, "
+                               "or not a JPEG), pil_fallback (a JPEG the native parser does not accept)")
 STAGE_TIME = REGISTRY.histogram("dv_stage_seconds", "per-batch GPU stage time from hipEvents (h2d, compute, d2h)",
                                 (0.0005, 0.001, 0.0025, 0.005, 0.01, 0.025, 0.05, 0.1, 0.25, 1.0))
 HOST_STAGE = REGISTRY.histogram("dv_host_stage_seconds",
