@@ -892,6 +892,7 @@ void tile_gather(Tensor x, Tensor xin, Tensor plan, Tensor shift, int64_t rank, 
   check_cuda(x, "x");
   c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
   check_plan(plan, shift);
+  check_cuda(xin, "xin");
   TORCH_CHECK(x.scalar_type() == at::kFloat && x.is_contiguous() && x.dim() == 4 && x.size(3) == 3, "tile_gather: x");
   TORCH_CHECK(xin.dim() == 4 && xin.size(3) == 8 && xin.is_contiguous(), "tile_gather: xin [U, Th, Tw, 8]");
   const int64_t U = xin.size(0);
@@ -919,7 +920,9 @@ void tile_pack(Tensor g, Tensor pack, Tensor plan, Tensor lpart, Tensor lcoef, i
               "tile_pack: pack too small / misaligned");
   TORCH_CHECK(lpart.scalar_type() == at::kFloat && lpart.is_contiguous() && lpart.dim() == 3 && lpart.size(1) == U,
               "tile_pack: lpart [L, U, LP]");
-  TORCH_CHECK(lcoef.scalar_type() == at::kFloat && lcoef.numel() == lpart.size(0), "tile_pack: lcoef [L]");
+  TORCH_CHECK(lcoef.scalar_type() == at::kFloat && lcoef.is_contiguous() && lcoef.numel() == lpart.size(0),
+              "tile_pack: lcoef [L]");
+  for (const Tensor* t : {&pack, &lpart, &lcoef}) check_cuda(*t, "tile_pack operand");
   check_rc(dv::tile_pack_launch(reinterpret_cast<const uint16_t*>(g.data_ptr()), reinterpret_cast<uint16_t*>(pack.data_ptr()),
                                 plan.data_ptr<int>(), lpart.data_ptr<float>(), lcoef.data_ptr<float>(), (int)lpart.size(0),
                                 (int)lpart.size(2), (int)U, (int)ucap, (int)rank, (int)world, (int)k0, (int)Th, (int)Tw,
@@ -939,9 +942,10 @@ void tile_update(Tensor packs, int64_t ucap, Tensor plan, Tensor shift, Tensor x
   const int64_t chunks = packs.numel() / (world * pe);
   TORCH_CHECK(chunks >= 1 && plan.size(0) <= chunks * world * ucap, "tile_update: plan larger than the packs");
   TORCH_CHECK(x.scalar_type() == at::kFloat && x.is_contiguous() && x.dim() == 4 && x.size(3) == 3, "tile_update: x");
-  TORCH_CHECK(done.scalar_type() == at::kByte && done.numel() == x.size(0) && loss.scalar_type() == at::kFloat &&
-                  loss.numel() == x.size(0),
+  TORCH_CHECK(done.scalar_type() == at::kByte && done.is_contiguous() && done.numel() == x.size(0) &&
+                  loss.scalar_type() == at::kFloat && loss.is_contiguous() && loss.numel() == x.size(0),
               "tile_update: done u8 [B], loss fp32 [B]");
+  for (const Tensor* t : {&x, &done, &loss}) check_cuda(*t, "tile_update operand");
   check_rc(dv::tile_update_launch(reinterpret_cast<const uint16_t*>(packs.data_ptr()), pe, (int)ucap, plan.data_ptr<int>(),
                                   (int)plan.size(0), shift.data_ptr<int>(), x.data_ptr<float>(), done.data_ptr<uint8_t>(),
                                   loss.data_ptr<float>(), (float)step, (float)max_loss, (int)world, (int)x.size(1),

@@ -104,7 +104,8 @@ def main(argv=None):
         sup = spawn_frontends(cfg, path, cfg.frontends)
         for sig in (signal.SIGTERM, signal.SIGINT):
             signal.signal(sig, lambda *_: stop.set())
-    info = pdist.init()
+    # the configured device decides (DV_DEVICE=cpu on a GPU box: CPU engine, Gloo), as it does in the service
+    info = pdist.init(device_type=torch.device(cfg.resolve_device()).type)
     eng = build_engine(cfg, info)
     if cfg.frontends > 0:
         try:
