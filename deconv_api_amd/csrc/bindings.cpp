@@ -583,6 +583,11 @@ std::string conv_route() {
   return out + b;
 }
 
+// The kernel the last seed_deconv3x3 / maxpool2x2 / unpool2x2 / deprocess_mosaic call on this thread chose:
+// "seed_deconv3x3 smallmap" | "seed_deconv3x3 grid", "maxpool2x2 vec" | "maxpool2x2 scalar", "unpool2x2 vec" |
+// "unpool2x2 scalar", "deprocess two-pass" | "deprocess stats+apply". "none": no such launch yet.
+std::string misc_route() { return dv::g_misc_route ? dv::g_misc_route : "none"; }
+
 // kind 0 max / 1 avg; dir 0 fwd (in=x, out=y) / 1 bwd (in=gy, out=gx); geom = N,H,W,C,OH,OW,k,s,pad.
 // x/gx and y/gy may be channel-slice views (dense pixels, channel stride 1, pixel stride % 8 == 0):
 // the InceptionV3 blocks pool straight out of / into their concat buffers. avgpool fwd may add a
@@ -1382,11 +1387,13 @@ void deprocess_mosaic(Tensor recon, Tensor out, int64_t tiles, bool reverse, c10
   TORCH_CHECK(out.scalar_type() == at::kByte && out.is_contiguous() && out.numel() == B * rows * H * 2 * W * 3,
               "deprocess: out [B, rows*H, 2*W, 3] u8");
   if (W % 4 != 0) {  // one block per image, two-pass statistics
+    dv::g_misc_route = "deprocess two-pass";
     check_rc(dv::deprocess_mosaic_launch(recon.data_ptr<float>(), out.data_ptr<uint8_t>(), (int)B, (int)H, (int)W,
                                          (int)tiles, reverse ? 1 : 0, cur_stream()),
              "deprocess_mosaic");
     return;
   }
+  dv::g_misc_route = "deprocess stats+apply";
   Tensor st;
   if (stats.has_value()) {  // {sum, sum^2} per image, from the final conv's epilogue
     TORCH_CHECK(stats->scalar_type() == at::kDouble && stats->is_contiguous() && stats->numel() == 2 * B &&
@@ -1634,6 +1641,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("relu_cols") = 0, py::arg("out2") = py::none(), py::arg("split_col") = 0,
         py::arg("obits") = py::none(), py::arg("ebits") = py::none(), py::arg("w_kw3") = py::none());
   m.def("conv_route", &conv_route, "kernel the last conv call on this thread launched (route report)");
+  m.def("misc_route", &misc_route, "kernel the last seed_deconv3x3 / maxpool2x2 / unpool2x2 / deprocess_mosaic call chose");
   m.def("conv_bpack", [] { return dv::g_route.bpack != 0; },
         "whether the last conv call on this thread staged its weights from the packed KW3 image (w_kw3)");
   m.def("conv_group_begin", &conv_group_begin, "start recording groupable small-problem convs (this thread)");

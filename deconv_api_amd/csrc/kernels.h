@@ -146,6 +146,11 @@ static inline void route_set(int kind, int bm, int bn, int stages, int ksplit, i
   g_route = ConvRoute{kind, bm, bn, stages, ksplit, epi, (g_route.flags & (CR_F_UNPOOL | CR_F_RELU_COPY)) | flags, 0, 0};
 }
 
+// The same for the multi-kernel launchers of misc.hip (seed_deconv3x3, maxpool2x2, unpool2x2) and for
+// bindings.cpp:deprocess_mosaic: the name of the kernel (pair) the last such call on this thread chose
+// (bindings.cpp misc_route()). One pointer store to a string literal on the launch path.
+extern __thread const char* g_misc_route;  // defined in misc.hip
+
 int conv_igemm_launch(const ConvArgs& a, int amode, int epi, hipStream_t stream);
 // LDS-DMA variant (FWD / TRANSPOSE, no mask): 8-wave 128x64-per-wave tiles
 int conv_dma_launch(const ConvArgs& a, int amode, int epi, hipStream_t stream);

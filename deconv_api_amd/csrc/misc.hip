@@ -8,6 +8,8 @@
 
 namespace dv {
 
+__thread const char* g_misc_route = nullptr;  // route report of the launchers below that choose a kernel (kernels.h)
+
 // ---------------------------------------------------------------------------------------
 // channel sums: sums[n][c] = sum_hw x[n][hw][c]   (reference: app/deepdream.py:369-380 sums
 // each filter's activation map; here per image, fp32 accumulate of the stored bf16 map).
@@ -219,6 +221,7 @@ int seed_deconv3x3_launch(const float* S, const int* f, const uint16_t* wt, uint
   const long long total = (long long)B * H * W * (Cin / 8);
   if (total >= (1LL << 31) || (long long)F * 9 * Cin >= (1LL << 31)) return -2;
   if ((long long)H * W <= kSeedMaxHW && Cin / 8 <= 256) {
+    g_misc_route = "seed_deconv3x3 smallmap";
     if (f16)
       hipLaunchKernelGGL(seed_deconv3x3_smallmap_kernel<DT_F16>, dim3((unsigned)B), dim3(256), 0, s, S, f, wt, out, H, W,
                          Cin, F);
@@ -228,6 +231,7 @@ int seed_deconv3x3_launch(const float* S, const int* f, const uint16_t* wt, uint
     return (int)hipGetLastError();
   }
   const long long blocks = std::min<long long>((total + 255) / 256, 256LL * 16);
+  g_misc_route = "seed_deconv3x3 grid";
   if (f16)
     hipLaunchKernelGGL(seed_deconv3x3_kernel<DT_F16>, dim3((unsigned)blocks), dim3(256), 0, s, S, f, wt, out, B, H, W,
                        Cin, F);
@@ -305,7 +309,8 @@ int seed_map_launch(const uint16_t* out4, const int* idx, const uint8_t* code, f
 // Mosaic + deprocess (reference: app/main.py:67-72 + app/deepdream.py:483-498):
 // the `tiles` reconstructions of one image form a 2x2 mosaic that is normalized as a whole:
 //   x = (x - mean) / (std + 1e-7) * 0.1 + 0.5 ; clip[0,1] ; *255 ; clip ; truncate to u8.
-// Mean/std are population statistics over the whole mosaic (two passes, fp64 block sums).
+// Mean/std are population statistics over the whole mosaic (two passes, fp64 block sums), for any
+// tiles in 1..4 and any H, W (an image's element count need not be a multiple of 4).
 // reverse_channels writes channel c at slot 2-c (OpenCV BGR encoder semantics for an RGB
 // encoder). One 1024-thread block per image.
 // ---------------------------------------------------------------------------------------
@@ -334,13 +339,21 @@ __global__ void __launch_bounds__(1024) deprocess_mosaic_kernel(const float* __r
   const long long per_tile = (long long)H * W * 3;
   const long long total = per_tile * tiles;
   const float* src = recon + (long long)b * total;
-  const float4* src4 = reinterpret_cast<const float4*>(src);
-  const long long n4 = total >> 2;  // total is a multiple of 4 (H*W*3*4)
+  // total = H*W*3*tiles is a multiple of 4 only with 4 tiles or an even H*W, and image b starts at element
+  // b * total of a 4-B aligned tensor: the 16-B loads cover the aligned middle of the image, the `head`
+  // elements before it (0..3) and the elements after its last whole float4 (0..3) are read one by one.
+  const int head = (int)min(total, (long long)((0 - (reinterpret_cast<uintptr_t>(src) >> 2)) & 3));
+  const float4* src4 = reinterpret_cast<const float4*>(src + head);
+  const long long n4 = (total - head) >> 2;
+  const int rest = head + (int)((total - head) & 3);  // scalar elements: head, then the tail
+  // (scalar element r is src[r] in the head and src[4 * n4 + r] in the tail, which starts at head + 4 * n4)
+  const long long ri = (int)threadIdx.x < head ? (long long)threadIdx.x : 4 * n4 + threadIdx.x;
   double s = 0.0;
   for (long long i = threadIdx.x; i < n4; i += 1024) {
     const float4 v = src4[i];
     s += (double)v.x + (double)v.y + (double)v.z + (double)v.w;
   }
+  if ((int)threadIdx.x < rest) s += (double)src[ri];
   const double mean_d = block_sum_d(s, sh) / (double)total;
   const float mean = (float)mean_d;
   double q = 0.0;
@@ -348,6 +361,10 @@ __global__ void __launch_bounds__(1024) deprocess_mosaic_kernel(const float* __r
     const float4 v = src4[i];
     const double a0 = v.x - mean, a1 = v.y - mean, a2 = v.z - mean, a3 = v.w - mean;
     q += a0 * a0 + a1 * a1 + a2 * a2 + a3 * a3;
+  }
+  if ((int)threadIdx.x < rest) {
+    const double a = src[ri] - mean;
+    q += a * a;
   }
   const float stdv = (float)sqrt(block_sum_d(q, sh) / (double)total);
   const float denom = stdv + 1e-7f;
@@ -721,6 +738,7 @@ int maxpool2x2_launch(const uint16_t* x, uint16_t* out, uint8_t* code, int N, in
       !(reinterpret_cast<uintptr_t>(x) & 15) && !(reinterpret_cast<uintptr_t>(out) & 15) &&
       !(reinterpret_cast<uintptr_t>(code) & 7)) {
     const long long blocks = std::min<long long>((total / 8 + 255) / 256, 256LL * 32);
+    g_misc_route = "maxpool2x2 vec";
     if (f16)
       hipLaunchKernelGGL(maxpool2x2_vec_kernel<DT_F16>, dim3((unsigned)blocks), dim3(256), 0, s, x, out, code, N, H, W, C);
     else
@@ -728,6 +746,7 @@ int maxpool2x2_launch(const uint16_t* x, uint16_t* out, uint8_t* code, int N, in
     return (int)hipGetLastError();
   }
   const long long blocks = std::min<long long>((total + 255) / 256, 4096);
+  g_misc_route = "maxpool2x2 scalar";
   if (f16) hipLaunchKernelGGL(maxpool2x2_kernel<DT_F16>, dim3((unsigned)blocks), dim3(256), 0, s, x, out, code, N, H, W, C);
   else hipLaunchKernelGGL(maxpool2x2_kernel<DT_BF16>, dim3((unsigned)blocks), dim3(256), 0, s, x, out, code, N, H, W, C);
   return (int)hipGetLastError();
@@ -791,12 +810,14 @@ int unpool2x2_launch(const uint16_t* p, const uint8_t* code, uint16_t* out, int 
   if (C % 8 == 0) {
     const long long total = (long long)N * (H / 2) * (W / 2) * (C / 8);
     const long long blocks = std::min<long long>((total + 255) / 256, 256LL * 32);
+    g_misc_route = "unpool2x2 vec";
     hipLaunchKernelGGL(unpool2x2_vec_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p, code, out, N, H, W, C,
                        code_div, relu);
     return (int)hipGetLastError();
   }
   const long long total = (long long)N * H * W * C;
   const long long blocks = std::min<long long>((total + 255) / 256, 8192);
+  g_misc_route = "unpool2x2 scalar";
   hipLaunchKernelGGL(unpool2x2_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p, code, out, N, H, W, C, code_div,
                      relu);
   return (int)hipGetLastError();

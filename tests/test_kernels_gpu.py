@@ -708,18 +708,23 @@ def test_seed_deconv(native_lib):
     gb = ops.seed_deconv3x3(Sb.to(DEV), fb.to(DEV), wt.to(DEV))
     for i in (0, 511, 1023):
         assert _rel(gb[i:i + 1], ops.seed_deconv3x3(Sb[i:i + 1], fb[i:i + 1], wt)) < 1e-2
-    # the one-workgroup-per-signal small-map kernel (default at <= 4096 px) == the grid-stride kernel
-    os.environ["DV_SEED_V1"] = "1"
-    try:
-        g1 = ops.seed_deconv3x3(Sb.to(DEV), fb.to(DEV), wt.to(DEV))
-        w64 = wt[..., :64].contiguous()
-        h1 = ops.seed_deconv3x3(S.to(DEV), f.to(DEV), w64.to(DEV))
-    finally:
-        del os.environ["DV_SEED_V1"]
-    # (same taps in the same order; the compilers' FMA contraction differs between the two bodies, so
-    # a value may differ in its last bf16 bit)
-    assert _rel(g1, gb) < 4e-3
-    assert _rel(h1, ops.seed_deconv3x3(S.to(DEV), f.to(DEV), w64.to(DEV))) < 4e-3  # Cin 64: 32 pixel groups
+    # the one-workgroup-per-signal small-map kernel (maps of <= 4096 px) == the grid-stride kernel (larger
+    # maps; the launcher chooses by shape alone, there is no switch). A 64 x 64 map takes the first; the
+    # same map with a 65th row of zeros takes the second, and a zero row is what the padding supplies, so
+    # rows 0..63 of the two results are the same sums.
+    misc_route = ops.native.lib().misc_route
+    for cin in (512, 64):  # Cin 64: 32 pixel groups per workgroup
+        wc = wt[:16, ..., :cin].contiguous().to(DEV)
+        fs = torch.tensor([0, 5, 15, -1, 7, 3], dtype=torch.int32).to(DEV)
+        S64 = torch.relu(torch.randn(6, 64, 64, generator=g))
+        small = ops.seed_deconv3x3(S64.to(DEV), fs, wc)
+        assert misc_route() == "seed_deconv3x3 smallmap"
+        grid = ops.seed_deconv3x3(torch.cat([S64, torch.zeros(6, 1, 64)], 1).to(DEV), fs, wc)
+        assert misc_route() == "seed_deconv3x3 grid"
+        # (same taps in the same order; the compilers' FMA contraction differs between the two bodies, so
+        # a value may differ in its last bf16 bit)
+        assert _rel(grid[:, :64], small) < 4e-3
+        assert _rel(small[:1], ops.seed_deconv3x3(S64[:1], fs[:1].cpu(), wc.cpu())) < 1e-2
 
 
 @pytest.mark.parametrize("pool", [False, True])
