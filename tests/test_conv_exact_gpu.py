@@ -18,7 +18,7 @@ import torch.nn.functional as F
 
 from deconv_api_amd import ops
 from deconv_api_amd.ops import autograd as AG
-from exact_helpers import BF, DEV, HF, _check_exact, _dev, _gen, _ints, _same, _signs, _weights
+from exact_helpers import BF, DEV, HF, _check_exact, _dev, _gen, _geom, _ints, _pool_case, _same, _signs, _weights
 from gpu_helpers import cus as _cus, route as _route, tune as _tune
 
 pytestmark = pytest.mark.gpu
@@ -199,19 +199,6 @@ DMA_CFGS = {1: (256, 256, 2), 2: (128, 256, 3), 3: (128, 128, 2), 4: (256, 128, 
 DMA_WIDTH = {64: (32, 40, False), 128: (24, 128, False), 256: (32, 256, True)}
 
 
-def _geom(M, even=False):
-    """Output geometry (N, OH, OW, crop) with N OH OW == M: both sides >= 3 (even sides for the pool
-    epilogue) where M factors that way. Where it does not (M = 127, 199, 257, 1543, ...), one output row
-    of M pixels (two for the pool) CROPPED from an input two rows taller (pad_h = 0, ``crop``): every
-    output still sums all three kernel rows of real data, so the density conditions hold there too."""
-    unit = 4 if even else 1
-    q = M // unit
-    for h in range(int(q ** 0.5), 2, -1):
-        if q % h == 0:
-            return (1, 2 * h, 2 * (q // h), False) if even else (1, h, q // h, False)
-    return (1, 2, M // 2, True) if even else (1, 1, M, True)
-
-
 @pytest.mark.parametrize("dt", [BF, HF])
 @pytest.mark.parametrize("cfg", sorted(DMA_CFGS))
 def test_exact_dma_tile_matrix(native_lib, cfg, dt):
@@ -282,19 +269,6 @@ def test_exact_dma_tile_misfit_raises(native_lib, cfg):
 # ----------------------------------------------------------------------------------------
 # fused pool epilogues on ties
 # ----------------------------------------------------------------------------------------
-
-def _pool_case(g, N, H, W, C, OC, taps=96):
-    x = _ints(g, (N, H, W, C), -3, 3)
-    cw = _weights(g, OC, C, taps=taps)
-    rp, rc = ops.conv2d(x, cw, relu=True, epilogue="pool")
-    full = ops.conv2d(x, cw, relu=True)
-    _check_exact(full, BF, x, cw, 4.0)
-    win = full.view(N, H // 2, 2, W // 2, 2, OC).permute(0, 1, 3, 2, 4, 5).reshape(N, H // 2, W // 2, 4, OC)
-    top2 = win.topk(2, dim=3).values
-    # (half of the outputs are 0 after the ReLU: one window in 16 is all zeros, and more tie above zero)
-    assert float((top2[..., 0, :] == top2[..., 1, :]).float().mean()) >= 0.05, "too few tied windows"
-    return x, cw, rp, rc
-
 
 @pytest.mark.parametrize("epi", ["pool_t", "pool_lds", "pool"])
 @pytest.mark.parametrize("N,H,W,C,OC,cfg,tile", [(2, 16, 14, 64, 128, 4, "256x128 st3"), (3, 10, 14, 64, 192, 6, "512x64 st2"),

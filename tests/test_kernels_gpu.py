@@ -648,16 +648,17 @@ def test_conv_halo_kernel(native_lib, N, H, W, C, OC, unpool, epi):
         Cm.set_policy(**old)
     assert got.shape == ref.shape and _rel(got, ref) < 1e-2
     if unpool and OC == 64 and epi == "bf16":  # v2 (register-resident weights) vs v1: same math
-        import os
-
-        os.environ["DV_HALO_V1"] = "1"
+        # v2 needs 16-B aligned output rows (out_ld % 8 == 0): the same problem written through a 64-channel
+        # slice of a 68-channel buffer takes the weight-in-LDS persistent kernel (v1)
+        wide = torch.zeros(N, H, W, 68, dtype=torch.bfloat16, device=DEV)
+        Cm.set_policy(impl="halo")
         try:
-            Cm.set_policy(impl="halo")
-            v1 = ops.conv2d(x.to(torch.bfloat16).to(DEV), cw.to_device(DEV), **kw)
+            v1 = ops.conv2d(x.to(torch.bfloat16).to(DEV), cw.to_device(DEV), out=wide[..., :64], **kw)
+            assert _route() == "halo_v1 persist", _route()
         finally:
-            del os.environ["DV_HALO_V1"]
             Cm.set_policy(**old)
-        assert _rel(got, v1) < 1e-2
+        assert v1.shape == got.shape and _rel(got, v1) < 1e-2
+        assert bool((wide[..., 64:] == 0).all())
 
 
 def test_conv_channel_slices(native_lib):
