@@ -167,7 +167,8 @@ def create_app(service=None, cfg: Optional[Config] = None, dream_service=None) -
     @app.post("/deepdream", openapi_extra=_FORM_SCHEMA)
     async def deepdream(request: Request):
         """Extension (not in the reference): DeepDream of the uploaded image. Form fields: file,
-        optional model (inception_v3 | resnet50), octaves, steps. Same data-URL conventions."""
+        optional model (inception_v3 | resnet50), octaves, steps, guide (a second image, same data-URL
+        conventions as file: the dream is pulled towards its features). Same data-URL conventions."""
         t0 = time.perf_counter()
         status = "200"
         try:
@@ -187,7 +188,10 @@ def create_app(service=None, cfg: Optional[Config] = None, dream_service=None) -
 
                 ds = state["dream"] = DreamService(cfg)
             try:
-                url = await ds.dream(form["file"], model, octaves, steps)
+                if form.get("guide"):
+                    url = await ds.dream(form["file"], model, octaves, steps, guide=form["guide"])
+                else:
+                    url = await ds.dream(form["file"], model, octaves, steps)
             except (ImageDecodeError, ValueError) as e:
                 status = "400"
                 return JSONResponse(status_code=400, content={"detail": str(e)})

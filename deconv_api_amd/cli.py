@@ -2,11 +2,13 @@
 
     python -m deconv_api_amd.cli deconv photo.jpg [more.png ...] --layer block5_conv3 [--out-dir out/]
     python -m deconv_api_amd.cli dream photo.jpg --model inception_v3 --octaves 4 --steps 20 [--out-dir out/]
+                                       [--guide other.jpg]
     python -m deconv_api_amd.cli layers
 
 ``deconv`` writes ``<stem>_<layer>.jpg``: the 2x2 mosaic of the top-4 deconvnet reconstructions, the same
 image ``POST /`` returns as a data URL (reference: app/main.py:45-78), all files as one batch on the device.
-``dream`` writes ``<stem>_dream_<model>.jpg`` (``POST /deepdream``). Configuration as the server's
+``dream`` writes ``<stem>_dream_<model>.jpg`` (``POST /deepdream``); with ``--guide`` every image dreams towards
+that image's features (the route's ``guide`` field). Configuration as the server's
 (``DV_*`` variables, config.py) with ``--device`` / ``--dtype`` / ``--weights`` overrides.
 """
 from __future__ import annotations
@@ -70,7 +72,8 @@ def cmd_dream(a, cfg) -> int:
     imgs = _read(a.images)
     ds = DreamService(cfg)
     try:
-        outs = [ds.run_batch([ds.prepare(img, a.octaves)], a.model, a.octaves, a.steps)[0] for img in imgs]
+        guides = [ds.prepare_guide(_read([a.guide])[0])] if a.guide else None
+        outs = [ds.run_batch([ds.prepare(img, a.octaves)], a.model, a.octaves, a.steps, guides)[0] for img in imgs]
     finally:
         ds.close()
     os.makedirs(a.out_dir, exist_ok=True)
@@ -107,6 +110,7 @@ def main(argv=None) -> int:
     r.add_argument("--model", default="inception_v3", choices=["inception_v3", "resnet50"])
     r.add_argument("--octaves", type=int, default=4)
     r.add_argument("--steps", type=int, default=20)
+    r.add_argument("--guide", default=None, help="dream towards this image's features (guided DeepDream)")
     r.add_argument("--out-dir", default=".")
     sub.add_parser("layers", help="the VGG16 layer names POST / accepts")
     a = ap.parse_args(argv)

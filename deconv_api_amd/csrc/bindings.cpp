@@ -810,6 +810,67 @@ void sumsq_core_bwd(Tensor x, Tensor scale, Tensor gx, int64_t b, c10::optional<
            "sumsq_core_bwd");
 }
 
+// Guided DeepDream loss (dream_guide.hip): a [N,H,W,C] against the guide features y [G,Q,C] of guide gidx[n]
+// (int32 [N], values < G: validated by the caller on the host where gidx is built - no sync here; the kernel
+// clamps). part [N, P <= 32] (optional) <- block partials of the matched scores over the border-b core;
+// gx (optional, like a) <- addend + scale[n] * y[q*] * (mask ? a > 0 : 1) on the core, addend (or 0) elsewhere.
+void guide_match(Tensor a, Tensor y, Tensor gidx, Tensor scale, c10::optional<Tensor> gx, int64_t b,
+                 c10::optional<Tensor> addend, c10::optional<Tensor> part, bool mask) {
+  check_cuda(a, "a");
+  check_cuda(y, "y");
+  check_cuda(gidx, "gidx");
+  check_cuda(scale, "scale");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(a.device());
+  TORCH_CHECK(a.dim() == 4 && a.is_contiguous() && a.size(3) % 32 == 0 && a.numel() > 0,
+              "guide_match: a contiguous NHWC, C % 32 == 0");
+  const int64_t N = a.size(0), H = a.size(1), W = a.size(2), C = a.size(3);
+  TORCH_CHECK(y.dim() == 3 && y.is_contiguous() && y.scalar_type() == a.scalar_type() && y.size(2) == C &&
+                  y.size(0) >= 1 && y.size(1) >= 1 && y.device() == a.device(),
+              "guide_match: y contiguous [G, Q, C] of a's dtype and device");
+  TORCH_CHECK(gidx.dim() == 1 && gidx.scalar_type() == at::kInt && gidx.is_contiguous() && gidx.size(0) == N &&
+                  gidx.device() == a.device(),
+              "guide_match: gidx int32 [N]");
+  TORCH_CHECK(scale.scalar_type() == at::kFloat && scale.is_contiguous() && scale.numel() == N &&
+                  scale.device() == a.device(),
+              "guide_match: scale [N] fp32");
+  TORCH_CHECK(b >= 0 && 2 * b < std::min(H, W), "guide_match: 2 b < min(H, W)");
+  TORCH_CHECK(gx.has_value() || part.has_value(), "guide_match: nothing to write (gx and part both absent)");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(a.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(y.data_ptr()) % 16 == 0,
+              "guide_match: 16-B aligned a, y");
+  uint16_t* gp = nullptr;
+  if (gx.has_value()) {
+    check_cuda(*gx, "gx");
+    TORCH_CHECK(gx->sizes() == a.sizes() && gx->scalar_type() == a.scalar_type() && gx->is_contiguous() &&
+                    gx->device() == a.device() && reinterpret_cast<uintptr_t>(gx->data_ptr()) % 16 == 0,
+                "guide_match: gx like a");
+    gp = reinterpret_cast<uint16_t*>(gx->data_ptr());
+  }
+  const uint16_t* ap = nullptr;
+  if (addend.has_value()) {
+    check_cuda(*addend, "addend");
+    TORCH_CHECK(gx.has_value(), "guide_match: addend without gx");
+    TORCH_CHECK(addend->sizes() == a.sizes() && addend->scalar_type() == a.scalar_type() && addend->is_contiguous() &&
+                    addend->device() == a.device() && reinterpret_cast<uintptr_t>(addend->data_ptr()) % 16 == 0,
+                "guide_match: addend like a");
+    ap = reinterpret_cast<const uint16_t*>(addend->data_ptr());
+  }
+  float* pp = nullptr;
+  int parts = dv::GUIDE_MAX_PARTS;  // the grid's parts; with part: one block per column, every column written
+  if (part.has_value()) {
+    check_cuda(*part, "part");
+    TORCH_CHECK(part->dim() == 2 && part->scalar_type() == at::kFloat && part->is_contiguous() && part->size(0) == N &&
+                    part->size(1) >= 1 && part->size(1) <= dv::GUIDE_MAX_PARTS && part->device() == a.device(),
+                "guide_match: part [N, P] fp32, 1 <= P <= 32");
+    parts = (int)part->size(1);
+    pp = part->data_ptr<float>();
+  }
+  check_rc(dv::guide_match_launch(reinterpret_cast<const uint16_t*>(a.data_ptr()),
+                                  reinterpret_cast<const uint16_t*>(y.data_ptr()), gidx.data_ptr<int>(),
+                                  scale.data_ptr<float>(), ap, gp, pp, parts, (int)N, (int)H, (int)W, (int)C,
+                                  (int)y.size(1), (int)y.size(0), (int)b, mask ? 1 : 0, dt_of(a), cur_stream()),
+           "guide_match");
+}
+
 // Fused DeepDream update (engine/deepdream.py): g [N,H,W,8] 16-bit input gradient, x [N,H,W,3] fp32
 // master image (updated in place), xin [N,H,W,8] next network input, gpart [N, P] scratch, lpart
 // [L, N, LP] sumsq partials of the L loss layers, lcoef [L] fp32 coefficient / numel, done u8 [N],
@@ -1657,6 +1718,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("stem_conv", &stem_conv, "strided few-channel stem conv (direct VALU kernels), fwd (dir 0) / dgrad (dir 1)");
   m.def("sumsq_core_bwd", &sumsq_core_bwd, "DeepDream loss gradient (+ optional addend)", py::arg("x"),
         py::arg("scale"), py::arg("gx"), py::arg("b"), py::arg("addend") = py::none(), py::arg("part") = py::none());
+  m.def("guide_match", &guide_match, "guided DeepDream loss: MFMA feature matching, loss partials + gradient",
+        py::arg("a"), py::arg("y"), py::arg("gidx"), py::arg("scale"), py::arg("gx") = py::none(), py::arg("b") = 0,
+        py::arg("addend") = py::none(), py::arg("part") = py::none(), py::arg("mask") = false);
   m.def("tile_gather", &tile_gather, "tiled DeepDream: rolled tile gather into the 16-bit network input", py::arg("x"),
         py::arg("xin"), py::arg("plan"), py::arg("shift"), py::arg("rank"), py::arg("world"), py::arg("k0") = 0);
   m.def("tile_pack", &tile_pack, "tiled DeepDream: owned-pixel gradient pack + unit loss / sum|g| tail", py::arg("g"),

@@ -251,6 +251,14 @@ int sumsq_core_bwd_launch(const uint16_t* x, const float* scale, const uint16_t*
 // sumsq_core_bwd + the forward partials (part [N][parts], as sumsq_core) in one pass
 int sumsq_core_fused_launch(const uint16_t* x, const float* scale, const uint16_t* addend, uint16_t* gx, float* part,
                             int parts, int N, int H, int W, int C, int b, int dtype, hipStream_t s);
+// guided DeepDream loss (dream_guide.hip): a [N,H,W,C] matched against the guide features y [G,Q,C] of guide
+// gidx[n]; per core position the best-scoring guide row q* (lowest q on ties). part [N][parts] (optional) gets
+// the block partials of sum_p s[p][q*], gx (optional) = addend + scale[n] * y[q*] * (mask ? a > 0 : 1) on the
+// core and addend (or 0) on the border. C % 32 == 0, parts <= GUIDE_MAX_PARTS; < 0: refused
+constexpr int GUIDE_MAX_PARTS = 32;
+int guide_match_launch(const uint16_t* a, const uint16_t* y, const int* gidx, const float* scale,
+                       const uint16_t* addend, uint16_t* gx, float* part, int parts, int N, int H, int W, int C, int Q,
+                       int G, int b, int mask, int dtype, hipStream_t s);
 // col2im of a strided conv's input gradient for <= 8 input channels (output padded to 8 channels)
 struct Col2ImGeom {
   int N, H, W, OH, OW, KH, KW, stride, pad_h, pad_w, Cr, J_ld;

@@ -32,7 +32,7 @@ from .. import knobs
 from ..ops import native
 from ..runtime.capture import capture
 from ..utils.logging import get_logger
-from ..ops.autograd import loss_tap, premasked_grads, sumsq_core
+from ..ops.autograd import _is_relu_out, guide_core, guide_index, guide_tap, loss_tap, premasked_grads, sumsq_core
 
 # DV_DREAM_FUSED=0: the step tail (loss, normalization, update) as torch ops instead of the fused
 # HIP kernels (A/B); DV_DREAM_GRAPHS: hipGraph cache entries (octave shapes) kept, LRU-evicted
@@ -90,6 +90,7 @@ class DreamSettings:
     iterations: int = 20
     max_loss: Optional[float] = 10.0
     border: int = 2  # act[:, 2:-2, 2:-2, :]
+    guide_size: int = 224  # a guide image is resized to this side before its features are taken
 
 
 def resize(x: torch.Tensor, hw: Tuple[int, int]) -> torch.Tensor:
@@ -98,6 +99,20 @@ def resize(x: torch.Tensor, hw: Tuple[int, int]) -> torch.Tensor:
         return x
     y = F.interpolate(x.permute(0, 3, 1, 2), size=hw, mode="bilinear", align_corners=True)
     return y.permute(0, 2, 3, 1).contiguous()
+
+
+@dataclass
+class GuideFeatures:
+    """A guided dream's targets: per loss layer the guide activations over the WHOLE map, ``feats[name]``
+    [G, Q, C] in the engine's dtype, and ``gidx`` (int32 [B]): the guide each image row dreams towards."""
+    feats: Dict[str, torch.Tensor]
+    gidx: torch.Tensor
+
+    def rows(self, lo: int, hi: int) -> "GuideFeatures":
+        return GuideFeatures(self.feats, self.gidx[lo:hi])
+
+    def key(self) -> tuple:
+        return tuple(tuple(f.shape) for f in self.feats.values())
 
 
 def inception_preprocess(img_u8: torch.Tensor) -> torch.Tensor:
@@ -128,37 +143,59 @@ class DeepDream:
     def _net_input(self, x: torch.Tensor) -> torch.Tensor:
         return F.pad(x, (0, 5)).to(self.dtype)
 
-    def loss(self, acts: Dict[str, torch.Tensor]) -> torch.Tensor:
+    def loss(self, acts: Dict[str, torch.Tensor], guide_feats: Optional[GuideFeatures] = None) -> torch.Tensor:
+        """Sum of squares of the loss layers' cores; with ``guide_feats`` the guided objective instead:
+        every core position's best dot product with the guide's feature vectors of that layer."""
         b = self.s.border
         total = None
         for name, coeff in self.s.layers.items():
             a = acts[name]
-            term = coeff * sumsq_core(a, b) / float(a[0].numel())
+            if guide_feats is None:
+                core = sumsq_core(a, b)
+            else:
+                core = guide_core(a, guide_feats.feats[name], guide_feats.gidx, b)
+            term = coeff * core / float(a[0].numel())
             total = term if total is None else total + term
         return total
 
-    def loss_and_grad(self, x: torch.Tensor):
+    def guide_features(self, guide: torch.Tensor, B: int) -> GuideFeatures:
+        """guide: preprocessed fp32 [G, h, w, 3] on the engine device, G = 1 (shared) or B. Resized to
+        guide_size x guide_size (every image of a batch gets the same Q per layer) and run through the
+        network once, without gradients."""
+        if guide.dim() != 4 or guide.shape[3] != 3 or guide.shape[0] not in (1, B):
+            raise ValueError(f"guide must be [1 or {B}, h, w, 3], got {tuple(guide.shape)}")
+        G = guide.shape[0]
+        gs = int(self.s.guide_size)
+        with torch.no_grad():
+            acts = self.net.forward(self._net_input(resize(guide.contiguous(), (gs, gs))), list(self.s.layers.keys()))
+            feats = {n: acts[n].detach().reshape(G, -1, acts[n].shape[3]).contiguous() for n in self.s.layers}
+        return GuideFeatures(feats, guide_index([0] * B if G == 1 else range(B), G, self.device))
+
+    def loss_and_grad(self, x: torch.Tensor, guide_feats: Optional[GuideFeatures] = None):
         """x: fp32 [B, H, W, 3] (preprocessed). Returns (loss [B], normalized grad [B, H, W, 3])."""
         xin = self._net_input(x).requires_grad_(True)
-        with premasked_grads():  # the loss gradient 2*act/numel vanishes where act does
+        # the loss gradient (2*act/numel, or the guide row masked by act > 0) vanishes where act does
+        with premasked_grads():
             acts = self.net.forward(xin, list(self.s.layers.keys()))
-        loss = self.loss(acts)
+        loss = self.loss(acts, guide_feats)
         (g,) = torch.autograd.grad(loss.sum(), xin)
         g = g[..., :3].float()
         g = g / g.abs().mean(dim=(1, 2, 3), keepdim=True).clamp_min(1e-7)
         return loss.detach(), g
 
-    def _step(self, x: torch.Tensor, done: torch.Tensor) -> torch.Tensor:
-        loss, g = self.loss_and_grad(x)
+    def _step(self, x: torch.Tensor, done: torch.Tensor, guide_feats: Optional[GuideFeatures] = None) -> torch.Tensor:
+        loss, g = self.loss_and_grad(x, guide_feats)
         if self.s.max_loss is not None:
             done |= loss > self.s.max_loss
         x.add_(g * ((~done).to(g.dtype) * self.s.step).view(-1, 1, 1, 1))
         return loss
 
     # ------------------------------------------------------------------ fused GPU step
-    def _state(self, B: int, hw: Tuple[int, int]):
+    def _state(self, B: int, hw: Tuple[int, int], gkey: Optional[tuple] = None):
         """Static buffers of one octave shape: fp32 master image x, the 16-bit network input xin
-        (an autograd leaf), loss/|g| partials, per-layer loss scales, done/loss flags."""
+        (an autograd leaf), loss/|g| partials, per-layer loss scales, done/loss flags; for a guided
+        dream (``gkey``: the layers' [G, Q, C]) also the guide features and the guide-of-row table,
+        which a captured graph reads: they are copied into before every replay."""
         dev = self.device
         names = list(self.s.layers.keys())
         st = type("DreamState", (), {})()
@@ -171,6 +208,10 @@ class DeepDream:
         st.lcoef = None  # filled on the first step (needs the activation shapes)
         st.scales = None
         st.graph = None
+        st.guide = None
+        if gkey is not None:
+            st.guide = GuideFeatures({n: torch.zeros(*shp, device=dev, dtype=self.dtype) for n, shp in zip(names, gkey)},
+                                     torch.zeros(B, dtype=torch.int32, device=dev))
         return st
 
     def _loss_grad(self, st, xin: torch.Tensor) -> torch.Tensor:
@@ -180,6 +221,7 @@ class DeepDream:
         lib = native.lib()
         names = list(self.s.layers.keys())
         b = self.s.border
+        guide = getattr(st, "guide", None)
         if st.scales is None:
             st.scales = {}
         tapped = set()
@@ -193,9 +235,13 @@ class DeepDream:
         def tap(name, a):
             a = a.contiguous()
             tapped.add(name)
-            return loss_tap(a, scale(name, a), b, st.lpart[names.index(name)] if FUSED_LOSS else None)
+            part = st.lpart[names.index(name)] if FUSED_LOSS else None
+            if guide is not None:
+                return guide_tap(a, guide.feats[name], guide.gidx, scale(name, a), b, part)
+            return loss_tap(a, scale(name, a), b, part)
 
-        with premasked_grads():  # the loss gradient 2*act/numel vanishes where act does
+        # the loss gradient (2*act/numel, or the guide row masked by act > 0) vanishes where act does
+        with premasked_grads():
             acts = self.net.forward(xin, names, tap=tap if TAPS else None)
         outs = [acts[n].contiguous() for n in names]
         if st.lcoef is None:
@@ -203,6 +249,17 @@ class DeepDream:
             st.lcoef = torch.tensor(coef, dtype=torch.float32, device=self.device)
         roots, gacts = [], []
         for i, (n, a) in enumerate(zip(names, outs)):
+            if guide is not None:  # one guide_match launch per layer: partials (+ the root's gradient)
+                y, relu = guide.feats[n], _is_relu_out(acts[n])
+                if n in tapped:
+                    if not FUSED_LOSS:
+                        lib.guide_match(a, y, guide.gidx, scale(n, a), None, b, None, st.lpart[i], relu)
+                    continue
+                ga = torch.empty_like(a)
+                lib.guide_match(a, y, guide.gidx, scale(n, a), ga, b, None, st.lpart[i], relu)
+                roots.append(a)
+                gacts.append(ga)
+                continue
             if n in tapped:  # its loss partials come from the tap's backward kernel (FUSED_LOSS)
                 if not FUSED_LOSS:
                     lib.sumsq_core(a, st.lpart[i], b)
@@ -227,13 +284,24 @@ class DeepDream:
         lib.dream_update(g.contiguous(), st.x, st.xin, st.gpart, st.lpart, st.lcoef, st.done, st.loss,
                          float(self.s.step), ml)
 
-    def _fused_state(self, B: int, hw: Tuple[int, int]):
+    def _load_guide(self, st, guide_feats: Optional[GuideFeatures]):
+        """This dream's guide into the state's static buffers (what its captured graph reads)."""
+        if guide_feats is not None:
+            with torch.no_grad():
+                for n, f in guide_feats.feats.items():
+                    st.guide.feats[n].copy_(f)
+                st.guide.gidx.copy_(guide_feats.gidx)
+        return st
+
+    def _fused_state(self, B: int, hw: Tuple[int, int], guide_feats: Optional[GuideFeatures] = None):
         steps = self.s.iterations if OCTAVE_GRAPH else 1
         key = (B, tuple(hw), steps, self._slot)
+        if guide_feats is not None:  # a guided graph has other launches and reads the guide buffers
+            key += ("guided", guide_feats.key())
         if key in self._graphs:
             self._graphs.move_to_end(key)
-            return self._graphs[key]
-        st = self._state(B, hw)
+            return self._load_guide(self._graphs[key], guide_feats)
+        st = self._load_guide(self._state(B, hw, None if guide_feats is None else guide_feats.key()), guide_feats)
         if self.use_graphs:
             s = torch.cuda.Stream(self.device)
             s.wait_stream(torch.cuda.current_stream(self.device))
@@ -281,17 +349,17 @@ class DeepDream:
             for _ in range(self.s.iterations // st.steps):
                 st.graph.replay()
 
-    def gradient_ascent(self, x: torch.Tensor) -> torch.Tensor:
+    def gradient_ascent(self, x: torch.Tensor, guide_feats: Optional[GuideFeatures] = None) -> torch.Tensor:
         B, H, W, _ = x.shape
         if self.fused:
-            st = self._fused_state(B, (H, W))
+            st = self._fused_state(B, (H, W), guide_feats)
             with torch.no_grad():
                 st.x.copy_(x)
                 st.xin.zero_()
                 st.xin[..., :3].copy_(x)
             self._ascend(st)
             return st.x.clone()
-        if self.use_graphs:
+        if self.use_graphs and guide_feats is None:  # (the guided torch-tail step runs eagerly)
             g, gx, gdone, gloss = self._graph(B, (H, W))
             gx.copy_(x)
             gdone.zero_()
@@ -301,7 +369,7 @@ class DeepDream:
         x = x.clone()
         done = torch.zeros(B, dtype=torch.bool, device=x.device)
         for _ in range(self.s.iterations):
-            self._step(x, done)
+            self._step(x, done, guide_feats)
         return x
 
     # ------------------------------------------------------------------ octaves
@@ -311,41 +379,46 @@ class DeepDream:
             shapes.append((int(H / self.s.octave_scale ** i), int(W / self.s.octave_scale ** i)))
         return shapes[::-1]
 
-    def run(self, x: torch.Tensor) -> torch.Tensor:
-        """x: preprocessed fp32 [B, H, W, 3] on the engine device -> dreamed fp32 image."""
+    def run(self, x: torch.Tensor, guide: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """x: preprocessed fp32 [B, H, W, 3] on the engine device -> dreamed fp32 image. ``guide``
+        (preprocessed fp32 [G, h, w, 3], G = 1 shared or G = B): dream towards the guide images - their
+        features are computed once here, not per octave."""
+        gf = None if guide is None else self.guide_features(guide, x.shape[0])
         n = self.split if (self.fused and x.is_cuda) else 1
         if n <= 1 or x.shape[0] < n:  # (uneven sub-batches allowed: x.chunk)
-            return self._run_one(x)
+            return self._run_one(x, gf)
         cur = torch.cuda.current_stream(self.device)
         while len(self._streams) < n:
             self._streams.append(torch.cuda.Stream(self.device))
         outs = []
         try:
+            lo = 0
             for i, xc in enumerate(x.chunk(n)):
                 st = self._streams[i]
                 st.wait_stream(cur)
                 with torch.cuda.stream(st):
                     self._slot = i
-                    outs.append(self._run_one(xc))
+                    outs.append(self._run_one(xc, None if gf is None else gf.rows(lo, lo + xc.shape[0])))
+                lo += xc.shape[0]
         finally:
             self._slot = 0
         for st in self._streams[:n]:
             cur.wait_stream(st)
         return torch.cat(outs)
 
-    def _run_one(self, x: torch.Tensor) -> torch.Tensor:
+    def _run_one(self, x: torch.Tensor, guide_feats: Optional[GuideFeatures] = None) -> torch.Tensor:
         img = x
-        for img in self.octave_steps(x):
+        for img in (self.octave_steps(x) if guide_feats is None else self.octave_steps(x, guide_feats)):
             pass
         return img
 
-    def octave_steps(self, x: torch.Tensor):
+    def octave_steps(self, x: torch.Tensor, guide_feats: Optional[GuideFeatures] = None):
         """Generator form of one (sub-)batch's dream: yields the image after each octave (its GPU
         work enqueued, not necessarily finished). The multi-rank service drives a dream octave by
         octave through this, polling each octave's completion under its failure deadlines and
         letting other commands run between octaves (parallel/sharded.py)."""
         if self.fused and x.is_cuda and OCTAVE_RESIZE:
-            yield from self._octave_steps_fused(x)
+            yield from self._octave_steps_fused(x, guide_feats)
             return
         shapes = self.octave_shapes(x.shape[1], x.shape[2])
         original = x
@@ -353,14 +426,14 @@ class DeepDream:
         img = x
         for hw in shapes:
             img = resize(img, hw)
-            img = self.gradient_ascent(img)
+            img = self.gradient_ascent(img) if guide_feats is None else self.gradient_ascent(img, guide_feats)
             upscaled = resize(shrunk, hw)
             same = resize(original, hw)
             img = img + (same - upscaled)
             shrunk = resize(original, hw)
             yield img
 
-    def _octave_steps_fused(self, x: torch.Tensor):
+    def _octave_steps_fused(self, x: torch.Tensor, guide_feats: Optional[GuideFeatures] = None):
         """``octave_steps`` on the fused GPU path: every octave transition is ONE octave_resize
         launch (csrc/dream.hip) that resizes (dreamed image + lost detail) straight into the next
         octave's static fp32 image and 16-bit network input, instead of F.interpolate x4, two ATen
@@ -384,7 +457,7 @@ class DeepDream:
 
         img = same = up = prev = None
         for o, hw in enumerate(shapes):
-            st = self._fused_state(B, hw)
+            st = self._fused_state(B, hw, guide_feats)
             # the octave's input: x resized (octave 0) or the previous octave's image + its detail
             lib.octave_resize(x if o == 0 else img, same, up, st.x, st.xin)
             cur = resized(x, hw)
@@ -398,10 +471,13 @@ class DeepDream:
         lib.octave_resize(img, same, up, out, None)
         yield out
 
-    def dream_u8(self, img_u8: torch.Tensor) -> torch.Tensor:
-        """uint8 RGB [B, H, W, 3] -> uint8 dreamed image."""
+    def dream_u8(self, img_u8: torch.Tensor, guide_u8: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """uint8 RGB [B, H, W, 3] -> uint8 dreamed image; ``guide_u8`` (uint8 RGB [1 or B, h, w, 3]):
+        dream towards these images (see ``run``)."""
         x = inception_preprocess(img_u8.to(self.device))
-        return inception_deprocess(self.run(x))
+        if guide_u8 is None:
+            return inception_deprocess(self.run(x))
+        return inception_deprocess(self.run(x, inception_preprocess(guide_u8.to(self.device))))
 
 
 RESNET_LAYERS = {"conv3_block4_out": 0.5, "conv4_block3_out": 1.0, "conv4_block6_out": 1.5}
@@ -451,6 +527,11 @@ class TiledDeepDream(DeepDream):
         # collective that never returns. (Collectives captured inside an octave graph are covered by
         # polling the octave's completion event instead.)
         self.coll_wait = None
+
+    def run(self, x: torch.Tensor, guide: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if guide is not None:
+            raise ValueError("guide is not supported by the tiled engine")
+        return super().run(x)
 
     @staticmethod
     def _axis_tiles(L: int, tile: int):

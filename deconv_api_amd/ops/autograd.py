@@ -472,6 +472,94 @@ def sumsq_core(x: torch.Tensor, b: int) -> torch.Tensor:
     return (core * core).sum(dim=(1, 2, 3))
 
 
+GUIDE_PARTS = 32  # loss partials per image of the guided loss (csrc/kernels.h GUIDE_MAX_PARTS)
+
+
+def guide_index(gidx, G: int, device) -> torch.Tensor:
+    """int32 [N] guide-of-row table on ``device`` from host integers, validated here (the kernel
+    indexes y with it; the binding does not sync to look at device values)."""
+    rows = [int(i) for i in gidx]
+    if not rows or min(rows) < 0 or max(rows) >= G:
+        raise ValueError(f"guide index outside [0, {G})")
+    return torch.tensor(rows, dtype=torch.int32, device=device)
+
+
+def _guide_winners(a: torch.Tensor, y: torch.Tensor, gidx: torch.Tensor, b: int):
+    """(scores [N, P, Q] fp32, winner [N, P]) of the core positions of ``a`` against y[gidx]; the
+    lowest q wins a tie."""
+    N, H, W, C = a.shape
+    core = a[:, b:H - b, b:W - b, :].reshape(N, -1, C).float()
+    s = torch.einsum("npc,nqc->npq", core, y.float()[gidx.long()])
+    q = torch.arange(s.shape[2], device=s.device)
+    win = torch.where(s == s.max(dim=2, keepdim=True).values, q, s.shape[2]).min(dim=2).values
+    return s, win.clamp_max(s.shape[2] - 1)  # (a NaN row matches nothing: clamp keeps the gather in range)
+
+
+class _GuideCoreFn(torch.autograd.Function):
+    """Per-image guided loss sum_p max_q <a[p], y[q]> over the border-b core (fp32), HIP forward and
+    backward (csrc/dream_guide.hip); the backward recomputes the match instead of storing winners."""
+
+    @staticmethod
+    def forward(ctx, a, y, gidx, b: int, mask: bool):
+        a = a.contiguous()
+        N = a.shape[0]
+        core = (a.shape[1] - 2 * b) * (a.shape[2] - 2 * b)
+        part = torch.empty(N, max(1, min(GUIDE_PARTS, -(-core // 64))), dtype=torch.float32, device=a.device)
+        native.lib().guide_match(a, y, gidx, torch.ones(N, dtype=torch.float32, device=a.device), None, b, None, part,
+                                 mask)
+        ctx.b, ctx.mask = b, mask
+        ctx.save_for_backward(a, y, gidx)
+        return part.sum(dim=1)
+
+    @staticmethod
+    def backward(ctx, g):
+        a, y, gidx = ctx.saved_tensors
+        gx = torch.empty_like(a)
+        native.lib().guide_match(a, y, gidx, g.float().contiguous(), gx, ctx.b, None, None, ctx.mask)
+        return gx, None, None, None, None
+
+
+def guide_core(a: torch.Tensor, y: torch.Tensor, gidx: torch.Tensor, b: int) -> torch.Tensor:
+    """The guided DeepDream loss term of one layer, fp32 [N]: every position of the border-b core of
+    ``a`` [N, H, W, C] scores against the guide features ``y`` [G, Q, C] of guide ``gidx[n]`` (int32
+    [N], see ``guide_index``) and contributes its best score (lowest q on ties). GPU: the MFMA
+    matching kernel, whose gradient y[q*] is masked by a > 0 when ``a`` is a tagged ReLU output (the
+    premasked-gradient contract). CPU: plain torch, where autograd gives y[q*] - also the oracle."""
+    if a.is_cuda:
+        if a.dtype not in (torch.bfloat16, torch.float16) or a.shape[3] % 32 != 0:
+            raise ValueError("guide_core on the GPU needs a 16-bit activation with C % 32 == 0")
+        return _GuideCoreFn.apply(a, y.contiguous(), gidx, b, _is_relu_out(a))
+    s, win = _guide_winners(a, y, gidx, b)
+    return s.gather(2, win.unsqueeze(2)).squeeze(2).sum(dim=1)
+
+
+class _GuideTapFn(torch.autograd.Function):
+    """``_LossTapFn`` for the guided loss: identity forward; the backward adds scale[n] * y[q*]
+    (masked) on the core to the gradient from above in ONE guide_match launch, which also writes
+    the layer's loss partials into ``part``."""
+
+    @staticmethod
+    def forward(ctx, a, y, gidx, scale, b: int, part, mask: bool):
+        ctx.save_for_backward(a, y, gidx, scale)
+        ctx.b, ctx.part, ctx.mask = b, part, mask
+        return a.view_as(a)
+
+    @staticmethod
+    def backward(ctx, g):
+        a, y, gidx, scale = ctx.saved_tensors
+        gx = torch.empty_like(a)
+        native.lib().guide_match(a, y, gidx, scale, gx, ctx.b, g.contiguous(), ctx.part, ctx.mask)
+        return gx, None, None, None, None, None, None
+
+
+def guide_tap(a: torch.Tensor, y: torch.Tensor, gidx: torch.Tensor, scale: torch.Tensor, b: int,
+              part: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``loss_tap`` for the guided loss (GPU, contiguous a): ``a`` unchanged, its gradient gains
+    scale[n] * y[gidx[n], q*] on the core; the ReLU-output tag carries over."""
+    relu = _is_relu_out(a)
+    return _tag(_GuideTapFn.apply(a, y, gidx, scale, b, part, relu), relu)
+
+
 class _BottleneckFn(torch.autograd.Function):
     """ResNet bottleneck block y = ReLU(c3(ReLU(c2(ReLU(c1(x))))) + shortcut(x)) with a hand-written
     backward that needs no elementwise kernels. Under the premasked contract (premasked_grads):

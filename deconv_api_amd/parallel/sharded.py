@@ -198,6 +198,12 @@ class ShardedRunner:
             cur = torch.cuda.current_stream(info.device)
             self.comm_stream = independent_stream(info.device, [cur])
             self.in_stream = independent_stream(info.device, [cur, self.comm_stream])
+            if self.ring is not None:
+                # the ring probed its upload stream against its OWN compute stream, but this runner's engine
+                # runs on ``cur``: an upload stream that shares cur's hardware queue puts every batch's input
+                # behind the previous batch's engine work (whether it did depended on how many streams the
+                # process had created before)
+                self.ring.copy_stream = independent_stream(info.device, [cur, self.comm_stream, self.ring.back_stream])
         self._bid = 0
 
     @property

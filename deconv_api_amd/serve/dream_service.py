@@ -12,7 +12,10 @@ same result and rank 0 answers.
 Requests are batched: a request joins the pending list after decode + size validation; the GPU
 worker takes the oldest request and every pending one with the same (model, octaves, steps,
 H, W) key (waiting up to ``dream_window_ms`` for more, at most ``dream_max_batch``) and runs them
-as ONE DeepDream batch. Every image's loss, gradient normalisation and max-loss flag are per
+as ONE DeepDream batch. A request may carry a GUIDE image (guided DeepDream: the image dreams towards
+the guide's features, engine/deepdream.py): it is decoded and resized to the engine's ``guide_size`` on
+the codec threads, guided and unguided requests batch apart (``guided`` is part of the key), and the
+guides are stacked like the images. Guided dreams run on the untiled one-GPU engine only. Every image's loss, gradient normalisation and max-loss flag are per
 image (engine/deepdream.py), so batching is exact; the batch is padded to a power of two by
 repeating the last image so the per-(B, H, W) hipGraph cache sees few distinct batch sizes."""
 from __future__ import annotations
@@ -39,10 +42,11 @@ MODELS = ("inception_v3", "resnet50")
 @dataclass
 class _Req:
     img: torch.Tensor  # u8 [H, W, 3], already resized to <= MAX_SIDE
-    key: Tuple[Any, ...]  # (model, octaves, steps, H, W)
+    key: Tuple[Any, ...]  # (model, octaves, steps, H, W, guided)
     fut: asyncio.Future
     loop: asyncio.AbstractEventLoop
     t0: float = field(default_factory=time.perf_counter)
+    guide: Optional[torch.Tensor] = None  # u8 [guide_size, guide_size, 3] of a guided request
 
 
 def _bucket(n: int, cap: int) -> int:
@@ -169,6 +173,24 @@ class DreamService:
             raise ValueError(f"image too small for {octaves} octaves (smallest octave side {small:.0f} < 75)")
         return t.contiguous()
 
+    def prepare_guide(self, img: np.ndarray) -> torch.Tensor:
+        """Decoded RGB guide -> u8 [guide_size, guide_size, 3] (the size its features are taken at, so
+        every guide of a batch stacks)."""
+        from ..engine.deepdream import resize
+
+        gs = int(DreamSettings().guide_size)
+        t = torch.from_numpy(np.ascontiguousarray(img))
+        if tuple(t.shape[:2]) != (gs, gs):
+            t = resize(t.unsqueeze(0).float(), (gs, gs))[0].round().clamp(0, 255).to(torch.uint8)
+        return t.contiguous()
+
+    def check_guided(self, H: int, W: int) -> None:
+        """Guided dreams run on the untiled one-GPU engine only (ValueError: the route's 400)."""
+        if self.world > 1:
+            raise ValueError("guide is not supported by a multi-rank service")
+        if max(H, W) > self.cfg.dream_tile:
+            raise ValueError(f"guide is not supported by the tiled engine (image side > {self.cfg.dream_tile})")
+
     # ------------------------------------------------------------------ batching worker
     def _ensure_worker(self) -> None:
         with self._cv:
@@ -198,18 +220,29 @@ class DreamService:
             M.QUEUE_DEPTH.set(len(self._pending), route="/deepdream")
             return batch
 
-    def run_batch(self, imgs: List[torch.Tensor], model: str, octaves: int, steps: int) -> np.ndarray:
+    def run_batch(self, imgs: List[torch.Tensor], model: str, octaves: int, steps: int,
+                  guides: Optional[List[torch.Tensor]] = None) -> np.ndarray:
         """u8 [H, W, 3] images of one shape -> dreamed u8 [n, H, W, 3] (one engine batch): across
         every rank when the service has several, tiled on this GPU for sides > dream_tile, else the
-        untiled engine."""
+        untiled engine. ``guides``: one prepared guide (``prepare_guide``) per image."""
         with self._run_lock:
-            return self._run_batch(imgs, model, octaves, steps)
+            return self._run_batch(imgs, model, octaves, steps, guides)
 
-    def _run_batch(self, imgs: List[torch.Tensor], model: str, octaves: int, steps: int) -> np.ndarray:
+    def _run_batch(self, imgs: List[torch.Tensor], model: str, octaves: int, steps: int,
+                   guides: Optional[List[torch.Tensor]] = None) -> np.ndarray:
         n = len(imgs)
         t0 = time.perf_counter()
         H, W = imgs[0].shape[:2]
-        if self.world > 1:
+        if guides is not None:
+            if len(guides) != n:
+                raise ValueError("one guide per image")
+            self.check_guided(H, W)
+            e = self.engine(model, octaves, steps)
+            pad = _bucket(n, self.max_batch) - n
+            x = torch.stack(imgs + [imgs[-1]] * pad)
+            g = torch.stack(list(guides) + [guides[-1]] * pad)  # padding repeats the last guide
+            out = e.dream_u8(x, g)[:n].cpu().numpy()
+        elif self.world > 1:
             out = self.runner.dream(torch.stack(imgs), model, octaves, steps)
         elif max(H, W) > self.cfg.dream_tile:
             e = self.tiled(model, octaves, steps)
@@ -232,8 +265,9 @@ class DreamService:
                 return
             model, octaves, steps = batch[0].key[:3]
             self.batches.append(len(batch))
+            guides = [r.guide for r in batch] if batch[0].guide is not None else None
             try:
-                out = self.run_batch([r.img for r in batch], model, octaves, steps)
+                out = self.run_batch([r.img for r in batch], model, octaves, steps, guides)
             except Exception as exc:  # noqa: BLE001 - delivered to every request of the batch
                 for r in batch:
                     r.loop.call_soon_threadsafe(_resolve, r.fut, None, exc)
@@ -249,15 +283,22 @@ class DreamService:
             self._worker.join(timeout=30)
 
     # ------------------------------------------------------------------ request entry
-    async def dream(self, uri: str, model: str = "inception_v3", octaves: int = 4, steps: int = 20) -> str:
+    async def dream(self, uri: str, model: str = "inception_v3", octaves: int = 4, steps: int = 20,
+                    guide: Optional[str] = None) -> str:
+        """``guide`` (optional): data URL of the image to dream towards."""
         self.validate(model, octaves, steps)
         loop = asyncio.get_running_loop()
         img = await loop.run_in_executor(None, read_data_url, uri)
         t = await loop.run_in_executor(None, self.prepare, img, octaves)
+        g = None
+        if guide is not None:
+            self.check_guided(t.shape[0], t.shape[1])
+            g = await loop.run_in_executor(None, lambda: self.prepare_guide(read_data_url(guide)))
         fut = loop.create_future()
         self._ensure_worker()
         with self._cv:
-            self._pending.append(_Req(t, (model, octaves, steps, t.shape[0], t.shape[1]), fut, loop))
+            key = (model, octaves, steps, t.shape[0], t.shape[1], g is not None)
+            self._pending.append(_Req(t, key, fut, loop, guide=g))
             M.QUEUE_DEPTH.set(len(self._pending), route="/deepdream")
             self._cv.notify_all()
         out = await fut

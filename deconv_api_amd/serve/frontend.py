@@ -132,8 +132,16 @@ class RemoteService(_Remote):
 class RemoteDream(_Remote):
     """``DreamService.dream`` forwarded to the GPU owner (which validates and decodes)."""
 
-    async def dream(self, uri: str, model: str = "inception_v3", octaves: int = 4, steps: int = 20) -> str:
-        body = json.dumps({"model": model, "octaves": octaves, "steps": steps}).encode() + b"\n" + uri.encode()
+    async def dream(self, uri: str, model: str = "inception_v3", octaves: int = 4, steps: int = 20,
+                    guide: str = None) -> str:
+        """Body: JSON header, newline, the image's data URL and - for a guided dream - the guide's data URL
+        right behind it, its length in the header's ``guide_len`` (absent for an unguided request)."""
+        head = {"model": model, "octaves": octaves, "steps": steps}
+        tail = b""
+        if guide is not None:
+            tail = guide.encode()
+            head["guide_len"] = len(tail)
+        body = json.dumps(head).encode() + b"\n" + uri.encode() + tail
         loop = asyncio.get_running_loop()
 
         async def send(cb):

@@ -53,7 +53,7 @@ RESP = struct.Struct("<IHQ")
 DECONV, STATUS, METRICS, LAYERS, DREAM, DECONV_JPEG = 1, 2, 3, 4, 5, 6
 JPEG_HEAD = struct.Struct("<BBH")
 SOCK_BUF = 8 << 20
-MAX_DREAM_BODY = 256 << 20  # JSON header + data URL of one /deepdream request
+MAX_DREAM_BODY = 256 << 20  # JSON header + data URL (+ the guide's data URL) of one /deepdream request
 
 
 def socket_path(port: int, rank: int) -> str:
@@ -228,9 +228,21 @@ class IngestServer:
         except ValueError:
             reply(rid, 400, b"bad dream header")
             return
+        kw = {}
+        try:
+            glen = int(p.get("guide_len", 0))  # a guided dream: the guide's data URL ends the body
+        except (TypeError, ValueError, AttributeError):
+            glen = -1
+        if glen < 0 or glen > len(uri):
+            reply(rid, 400, b"bad dream header")
+            return
+        if glen:
+            uri, guide = uri[:-glen], uri[-glen:]
+            kw["guide"] = guide.decode("ascii", errors="replace")
         loop = self._dream_loop()
         fut = asyncio.run_coroutine_threadsafe(
-            self.dream.dream(uri.decode("ascii", errors="replace"), p["model"], int(p["octaves"]), int(p["steps"])), loop)
+            self.dream.dream(uri.decode("ascii", errors="replace"), p["model"], int(p["octaves"]), int(p["steps"]),
+                             **kw), loop)
 
         def done(f):
             e = f.exception()
