@@ -5,6 +5,7 @@
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 
+#include "conv_dma_plan.h"
 #include "jpeg_dec.h"
 #include "jpeg_enc.h"
 #include "kernels.h"
@@ -45,8 +46,74 @@ void check_rc(int rc, const char* what) {
   TORCH_CHECK(rc == 0, what, " launch failed with code ", rc);
 }
 
+// KW3P stream-K hand-off timeouts (conv_dma_impl.h): one process-wide counter in host-coherent pinned
+// memory, written by the kernel with a system-scope atomic, read by the host without any copy or sync
+static unsigned* sk_error_host() {
+  static unsigned* p = [] {
+    void* h = nullptr;
+    check_rc((int)hipHostMalloc(&h, 64, hipHostMallocCoherent | hipHostMallocMapped), "hipHostMalloc(sk errors)");
+    std::memset(h, 0, 64);
+    return reinterpret_cast<unsigned*>(h);
+  }();
+  return p;
+}
+static unsigned* sk_error_counter() {
+  unsigned* h = sk_error_host();
+  void* d = nullptr;
+  check_rc((int)hipHostGetDevicePointer(&d, h, 0), "hipHostGetDevicePointer(sk errors)");
+  return reinterpret_cast<unsigned*>(d);
+}
+int64_t sk_errors(bool reset) {
+  volatile unsigned* h = sk_error_host();
+  const unsigned v = *h;
+  if (reset) *h = 0u;
+  return (int64_t)v;
+}
+
+}  // namespace
+
+// compute units of the current device (cached per device): the one source of the CU count (kernels.h)
+int dv::device_cus() {
+  static std::mutex mu;
+  static std::map<int, int> cache;
+  int dev = 0;
+  check_rc((int)hipGetDevice(&dev), "hipGetDevice");
+  std::lock_guard<std::mutex> lk(mu);
+  auto it = cache.find(dev);
+  if (it != cache.end()) return it->second;
+  int cu = 0;
+  check_rc((int)hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev), "hipDeviceGetAttribute");
+  return cache[dev] = cu > 0 ? cu : 256;
+}
+
+namespace {
+
+// Launch a planned LDS-DMA conv on the current device and stream: the fp32 split-K workspace when the plan splits K,
+// the KW3P stream-K workspace (one fp32 partial-tile slot + one flag per CU) only when it streams, run, reduce.
+// Both come from the stream-ordered caching allocator (graph-capture safe; concurrent streams never share one).
+void launch_dma_plan(dv::ConvArgs a, const dv::DmaPlan& plan) {
+  check_rc(plan.status, "conv_dma");
+  const auto f32 = at::TensorOptions().dtype(at::kFloat).device(at::kCUDA);  // the current device
+  Tensor ws, skws;
+  if (plan.ksplit > 1) {
+    ws = at::empty({(int64_t)plan.ksplit * a.M * a.OCpad}, f32);
+    a.ws = ws.data_ptr<float>();
+    a.ksplit = plan.ksplit;
+  }
+  if (plan.sk) {
+    const int64_t cus = plan.cus;
+    skws = at::empty({cus * dv::kSkSlotFloats + cus}, f32);
+    a.skw = skws.data_ptr<float>();
+    a.skflag = reinterpret_cast<unsigned*>(a.skw + cus * dv::kSkSlotFloats);
+    a.skslots = (int)cus;
+    a.skerr = sk_error_counter();
+  }
+  check_rc(dv::conv_dma_run(a, plan, cur_stream()), "conv_dma");
+  if (plan.ksplit > 1) check_rc(dv::splitk_reduce_launch(a, plan.epi, cur_stream()), "splitk_reduce");
+}
+
 // Grouped launches (conv_group_begin / conv_group_end): between the two calls every conv that would
-// run on the LDS-DMA kernel with a groupable small-problem tile config (dv::conv_dma_group_cfg) is
+// run on the LDS-DMA kernel with a groupable small-problem tile config (DmaPlan::group_cfg) is
 // recorded instead of launched; the end call launches the recorded problems as grouped kernels of up
 // to kGroupMax problems per (A mode, epilogue, config, dtype), in recording order. The caller
 // guarantees the recorded convs are independent (no one reads what another writes) and keeps their
@@ -85,63 +152,14 @@ int64_t conv_group_end() {
       ps[n++] = pend[j].a;
       done[j] = true;
     }
-    if (n == 1) {  // nothing to run beside it: the one-problem path, with its split-K planning
-      dv::ConvArgs a = ps[0];
-      const int ks = dv::conv_dma_splitk(a);
-      Tensor ws;
-      if (ks > 1) {
-        int dev = 0;
-        check_rc((int)hipGetDevice(&dev), "hipGetDevice");
-        ws = at::empty({(int64_t)ks * a.M * a.OCpad}, at::TensorOptions().dtype(at::kFloat).device(at::kCUDA, dev));
-        a.ws = ws.data_ptr<float>();
-        a.ksplit = ks;
-      }
-      check_rc(dv::conv_dma_launch(a, pend[i].amode, pend[i].epi, cur_stream()), "conv_dma");
-      if (ks > 1) check_rc(dv::splitk_reduce_launch(a, pend[i].epi, cur_stream()), "splitk_reduce");
+    if (n == 1) {  // nothing to run beside it: the one-problem path, planned again (with its split-K)
+      launch_dma_plan(ps[0], dv::conv_dma_plan(ps[0], pend[i].amode, pend[i].epi));
     } else {
       check_rc(dv::conv_dma_group_launch(ps, n, pend[i].amode, pend[i].epi, cur_stream()), "conv_dma_group");
     }
     ++launches;
   }
   return launches;
-}
-
-// KW3P stream-K hand-off timeouts (conv_dma_impl.h): one process-wide counter in host-coherent pinned
-// memory, written by the kernel with a system-scope atomic, read by the host without any copy or sync
-static unsigned* sk_error_host() {
-  static unsigned* p = [] {
-    void* h = nullptr;
-    check_rc((int)hipHostMalloc(&h, 64, hipHostMallocCoherent | hipHostMallocMapped), "hipHostMalloc(sk errors)");
-    std::memset(h, 0, 64);
-    return reinterpret_cast<unsigned*>(h);
-  }();
-  return p;
-}
-static unsigned* sk_error_counter() {
-  unsigned* h = sk_error_host();
-  void* d = nullptr;
-  check_rc((int)hipHostGetDevicePointer(&d, h, 0), "hipHostGetDevicePointer(sk errors)");
-  return reinterpret_cast<unsigned*>(d);
-}
-int64_t sk_errors(bool reset) {
-  volatile unsigned* h = sk_error_host();
-  const unsigned v = *h;
-  if (reset) *h = 0u;
-  return (int64_t)v;
-}
-
-// compute units of the current device (cached per device)
-int64_t device_cus() {
-  static std::mutex mu;
-  static std::map<int, int64_t> cache;
-  int dev = 0;
-  check_rc((int)hipGetDevice(&dev), "hipGetDevice");
-  std::lock_guard<std::mutex> lk(mu);
-  auto it = cache.find(dev);
-  if (it != cache.end()) return it->second;
-  int cu = 0;
-  check_rc((int)hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev), "hipDeviceGetAttribute");
-  return cache[dev] = cu > 0 ? cu : 256;
 }
 
 // geom: N,H,W,C, OH,OW,OC,OCpad, KH,KW,stride,pad_h,pad_w, K,Kpad, M, relu,relu_in,accumulate,
@@ -276,18 +294,8 @@ int64_t conv(Tensor x, Tensor w, c10::optional<Tensor> bias, Tensor out, c10::op
     need(*res, ((int64_t)(a.M - 1) * a.res_ld + a.OC) * 2, "res");
     a.res = reinterpret_cast<const uint16_t*>(res->data_ptr());
     a.res_elems = avail_bytes(*res) / 2;
-    if (emask.has_value()) {
-      check_cuda(*emask, "emask");
-      TORCH_CHECK(emask->scalar_type() == dt && emask->dim() == 4 && emask->stride(3) == 1, "emask: x's dtype, NHWC");
-      a.emask_ld = emask->stride(2);
-      TORCH_CHECK(emask->stride(1) == a.OW * a.emask_ld && emask->stride(0) == (int64_t)a.OH * a.OW * a.emask_ld,
-                  "emask: pixels must be dense");
-      need(*emask, ((int64_t)(a.M - 1) * a.emask_ld + a.OC) * 2, "emask");
-      a.emask = reinterpret_cast<const uint16_t*>(emask->data_ptr());
-      a.emask_elems = avail_bytes(*emask) / 2;
-    }
   }
-  if (emask.has_value() && a.emask == nullptr) {  // output mask without a residual
+  if (emask.has_value()) {  // output mask (with or without a residual)
     check_cuda(*emask, "emask");
     TORCH_CHECK(emask->scalar_type() == dt && emask->dim() == 4 && emask->stride(3) == 1, "emask: x's dtype, NHWC");
     TORCH_CHECK(epi == dv::CONV_E_BF16 && impl != 1 && impl != 3, "emask: 16-bit epilogue on the LDS-DMA kernel only");
@@ -488,27 +496,18 @@ int64_t conv(Tensor x, Tensor w, c10::optional<Tensor> bias, Tensor out, c10::op
     // the DMA kernel addresses A with 32-bit offsets relative to the tile's first image
     const int64_t imgs_per_tile = 512 / std::max(1, a.OH * a.OW) + 2;
     TORCH_CHECK((int64_t)a.H * a.W * a.x_ld * 2 * imgs_per_tile < 0x7FFFFFF0LL, "conv dma: image too large");
+    // the plan (conv_dma_plan.h): tile or shared-tap kernel, split-K (plain epilogues only), stream-K, group config
+    const dv::DmaPlan plan = dv::conv_dma_plan(a, (int)amode, (int)epi);
     if (g_group_active && !g_group_paused && (impl == 0 || impl == 2) && !mask.has_value() && !unpooled.defined() &&
-        !relu_x.defined() && !a.ucode && !a.out2 && !stats.has_value()) {
-      const int cfg = dv::conv_dma_group_cfg(a, (int)amode, (int)epi);
-      if (cfg != 0) {  // recorded (no split-K: the group runs its problems side by side); launched by conv_group_end
-        g_group.push_back(PendingConv{a, (int)amode, (int)epi, cfg});
-        dv::g_route.kind = dv::CR_GROUP;
-        dv::g_route.cfg = cfg;
-        return 0;
-      }
+        !relu_x.defined() && !a.ucode && !a.out2 && !stats.has_value() && plan.group_cfg != 0) {
+      // recorded (no split-K: the group runs its problems side by side); launched by conv_group_end
+      g_group.push_back(PendingConv{a, (int)amode, (int)epi, plan.group_cfg});
+      dv::g_route.kind = dv::CR_GROUP;
+      dv::g_route.cfg = plan.group_cfg;
+      return 0;
     }
-    // split-K when the tile grid would leave most CUs idle (plain epilogues only)
-    // (the reduce kernel applies bias / ReLU / accumulate / residual / emask; not the unpool scatter)
-    const bool plain_epi = (epi == dv::CONV_E_BF16 || epi == dv::CONV_E_F32) && !a.ucode && !a.out2;
-    const int ks = plain_epi ? dv::conv_dma_splitk(a) : 1;
-    Tensor ws;
-    if (ks > 1) {
-      ws = at::empty({(int64_t)ks * a.M * a.OCpad}, x.options().dtype(at::kFloat));
-      a.ws = ws.data_ptr<float>();
-      a.ksplit = ks;
-    }
-    if (ks == 1 && (impl == 0 || impl == 2) && amode == dv::CONV_A_FWD && epi == dv::CONV_E_BF16 && !mask.has_value()) {
+    if (plan.ksplit == 1 && (impl == 0 || impl == 2) && amode == dv::CONV_A_FWD && epi == dv::CONV_E_BF16 &&
+        !mask.has_value()) {
       dv::ConvArgs ap = a;
       const int64_t flags = with_bits(ap);
       const int rc = dv::conv_pw_launch(ap, cur_stream());  // large-M 1x1 convs: persistent pipeline
@@ -518,23 +517,7 @@ int64_t conv(Tensor x, Tensor w, c10::optional<Tensor> bias, Tensor out, c10::op
         return flags;
       }
     }
-    // KW3P stream-K workspace (conv_dma_impl.h:kw3_sk_ok decides whether it is used): one fp32 partial-tile
-    // slot + one flag per CU, from the stream-ordered caching allocator (graph-capture safe; concurrent
-    // streams never share one)
-    Tensor skws;
-    const int64_t cus = device_cus();
-    if (ks == 1 && amode == dv::CONV_A_FWD && epi == dv::CONV_E_BF16 && !mask.has_value() && a.KH == 3 && a.KW == 3 &&
-        a.stride == 1 && a.pad_h == 1 && a.pad_w == 1 && a.C % 32 == 0 && a.OCpad % 128 == 0 && !a.res && !a.emask &&
-        !a.accumulate && (int64_t)a.M * a.OCpad > cus * dv::kSkSlotFloats && cus <= dv::kSkMaxWg &&
-        std::getenv("DV_NO_KW3_SK") == nullptr) {
-      skws = at::empty({cus * dv::kSkSlotFloats + cus}, x.options().dtype(at::kFloat));
-      a.skw = skws.data_ptr<float>();
-      a.skflag = reinterpret_cast<unsigned*>(a.skw + cus * dv::kSkSlotFloats);
-      a.skslots = (int)cus;
-      a.skerr = sk_error_counter();
-    }
-    check_rc(dv::conv_dma_launch(a, (int)amode, (int)epi, cur_stream()), "conv_dma");
-    if (ks > 1) check_rc(dv::splitk_reduce_launch(a, (int)epi, cur_stream()), "splitk_reduce");
+    launch_dma_plan(a, plan);
   } else {
     check_rc(dv::conv_igemm_launch(a, (int)amode, (int)epi, cur_stream()), "conv_igemm");
   }
@@ -545,43 +528,7 @@ int64_t conv(Tensor x, Tensor w, c10::optional<Tensor> bias, Tensor out, c10::op
 // The kernel the last conv / conv_stem_pool call on this thread launched, e.g. "dma 128x128 st2 ks1",
 // "kw3p 256x256 lds sk", "kw3 256x256 + dma 128x128 tail m_base=65536", "unpool2x2 > dma 64x64 st3 ks1",
 // "group cfg8" (recorded in an open conv group, launched by conv_group_end). "none": no launch recorded.
-std::string conv_route() {
-  const dv::ConvRoute r = dv::g_route;
-  static const char* const kEpi[] = {"", " reg", " lds", " unpool", " pool", " strips", " persist", " pool_t", " pool_lds"};
-  const char* epi = (r.epi >= 0 && r.epi <= 8) ? kEpi[r.epi] : "";
-  char b[160];
-  switch (r.kind) {
-    case dv::CR_IGEMM: std::snprintf(b, sizeof b, "igemm %dx%d", r.bm, r.bn); break;
-    case dv::CR_HALO_V1: std::snprintf(b, sizeof b, "halo_v1%s", epi); break;
-    case dv::CR_HALO_V2: std::snprintf(b, sizeof b, "halo_v2"); break;
-    case dv::CR_POOL_V3: std::snprintf(b, sizeof b, "pool_v3"); break;
-    case dv::CR_C8_STREAM: std::snprintf(b, sizeof b, "c8_stream"); break;
-    case dv::CR_HS16:
-    case dv::CR_HS32:
-      std::snprintf(b, sizeof b, "%s oc%d%s%s%s", r.kind == dv::CR_HS16 ? "hs16" : "hs32", r.bn, epi,
-                    (r.flags & dv::CR_F_OCSPLIT) ? " ocsplit" : "", r.cfg == 1 ? " stem" : "");
-      break;
-    case dv::CR_PW: std::snprintf(b, sizeof b, "pw %dx%d", r.bm, r.bn); break;
-    case dv::CR_DMA:
-      std::snprintf(b, sizeof b, "dma %dx%d st%d ks%d%s%s", r.bm, r.bn, r.stages, r.ksplit, epi,
-                    (r.flags & dv::CR_F_MASK) ? " mask" : "");
-      break;
-    case dv::CR_KW3:
-    case dv::CR_KW3P: {
-      int n = std::snprintf(b, sizeof b, "%s %dx%d%s%s", r.kind == dv::CR_KW3 ? "kw3" : "kw3p", r.bm, r.bn, epi,
-                            (r.flags & dv::CR_F_SK) ? " sk" : "");
-      if ((r.flags & dv::CR_F_TAIL) && n > 0 && n < (int)sizeof b)
-        std::snprintf(b + n, sizeof b - n, " + dma 128x128 tail m_base=%d", r.m_base);
-      break;
-    }
-    case dv::CR_GROUP: std::snprintf(b, sizeof b, "group cfg%d", r.cfg); break;
-    default: std::snprintf(b, sizeof b, "none"); break;
-  }
-  std::string out;
-  if (r.flags & dv::CR_F_UNPOOL) out += "unpool2x2 > ";
-  if (r.flags & dv::CR_F_RELU_COPY) out += "relu_copy > ";
-  return out + b;
-}
+std::string conv_route() { return dv::route_str(dv::g_route); }
 
 // The kernel the last seed_deconv3x3 / maxpool2x2 / unpool2x2 / deprocess_mosaic call on this thread chose:
 // "seed_deconv3x3 smallmap" | "seed_deconv3x3 grid", "maxpool2x2 vec" | "maxpool2x2 scalar", "unpool2x2 vec" |

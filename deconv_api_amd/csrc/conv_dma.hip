@@ -1,6 +1,6 @@
-// LDS-DMA implicit-GEMM conv: dispatch over (dtype, A mode, epilogue), split-K planning and
-// reduction, ReLU-masked dgrads and the tuning override. The kernel and its tile configs live in
-// conv_dma_impl.h (design notes there); the heavy dma_bn instantiations are in conv_dma_*.hip.
+// LDS-DMA implicit-GEMM conv, host side: the family's knobs (the only place it reads the environment), plan = knobs +
+// CU count + policy (conv_dma_plan.h), the dispatch of a plan over (dtype, A mode, epilogue) to the instantiation units
+// conv_dma_*.hip, the split-K reduction and the tuning override. The kernels live in conv_dma_impl.h (design notes there).
 #include "conv_dma_impl.h"
 
 namespace dv {
@@ -14,36 +14,44 @@ void conv_dma_tune(int cfg, int ks) {
   g_ks = ks;
 }
 
-// Split-K factor for a launch that would leave most CUs idle: small M (batch-1 serving, deep
-// layers of strong-scaled DeepDream tiles, dense layers) with a long K. 1 = no split.
-// The small-problem 64x64 tiles (auto_cfg 8: DeepDream's small octaves, replayed from hipGraphs)
-// split a long K into 2 / 4 parts: in a graph the extra reduce launch costs ~2 us while each K
-// tile of the serial K loop costs ~0.4 us (tools/small_conv_latency.py: M 1600 x N 160 x K 1440
-// 14.8 -> 11.4 us, M 4096 x N 96 x K 2592 23.3 -> 15.2 us; K <= 768 gains nothing).
-int conv_dma_splitk(const ConvArgs& a) {
-  if (g_ks > 0) return std::min(g_ks, a.Kpad / 64);
-  static const bool off = dv_ab_env("DV_NO_SPLITK") != nullptr;
-  static const bool small_off = dv_ab_env("DV_NO_SMALL_SPLITK") != nullptr;
-  if (off) return 1;
-  const int nk = a.Kpad / 64;
-  if (g_cfg == 0 && auto_cfg(a) == 8) {
-    // only the smallest problems: the reduce pass re-reads ks x M x OCpad fp32 partials, which
-    // outweighs the shorter K loop once M x OCpad grows (full-model A/B, docs/KERNELS.md)
-    static const long long mn_max =
-        dv_ab_env("DV_SMALL_SPLITK_MN") ? std::atoll(dv_ab_env("DV_SMALL_SPLITK_MN")) : 300000LL;
-    if (small_off || (long long)a.M * a.OCpad > mn_max) return 1;
-    return nk >= 20 ? 4 : (nk >= 16 ? 2 : 1);
+// Every switch of the family. The dispatch A/B switches are read per launch and only under DV_ABLATIONS=1
+// (a serving process keeps its dispatch whatever its environment holds); the tile / split-K thresholds are
+// latched at the first plan. DV_NO_KW3_SK is a production switch (ops/conv.py names it as the recovery
+// from a stream-K hand-off timeout), read per launch.
+static DmaKnobs dma_knobs() {
+  static const bool no_auto_cfg = dv_ab_env("DV_NO_AUTO_CFG") != nullptr;  // A/B: the size-based choice only
+  static const int kmin = dv_ab_env("DV_SMALL_TILE_KMIN") ? std::atoi(dv_ab_env("DV_SMALL_TILE_KMIN")) : 0;
+  static const bool no_splitk = dv_ab_env("DV_NO_SPLITK") != nullptr;
+  static const bool no_small_splitk = dv_ab_env("DV_NO_SMALL_SPLITK") != nullptr;
+  static const long long mn = dv_ab_env("DV_SMALL_SPLITK_MN") ? std::atoll(dv_ab_env("DV_SMALL_SPLITK_MN")) : 300000LL;
+  DmaKnobs k;
+  k.no_auto_cfg = no_auto_cfg; k.small_tile_kmin = kmin; k.no_splitk = no_splitk; k.no_small_splitk = no_small_splitk;
+  k.small_splitk_mn = mn; k.cfg = g_cfg; k.ks = g_ks;
+  k.no_kw3_sk = std::getenv("DV_NO_KW3_SK") != nullptr;
+  if (!dv_ablations_on()) return k;
+  auto is = [](const char* e, const char* v) { return e != nullptr && std::strcmp(e, v) == 0; };
+  if (const char* e = dv_ab_env("DV_KW3")) k.kw3 = std::atoi(e);
+  if (const char* e = dv_ab_env("DV_KW3_VAR")) k.kw3_var = std::atoi(e);
+  if (const int v = k.kw3_var; v == 8 || v == 9 || v == 10 || v == 20 || v == 21) {
+    // timing ablations with wrong outputs: a stray DV_KW3_VAR in a serving process cannot corrupt convs
+    const bool allow = dv_ab_env("DV_ALLOW_WRONG_ABLATION") != nullptr;
+    static bool warned = false;
+    if (!warned)
+      fprintf(stderr, allow ? "deconv_api_amd: DV_KW3_VAR=%d: timing ablation, outputs are WRONG\n"
+                            : "deconv_api_amd: DV_KW3_VAR=%d ignored (needs DV_ALLOW_WRONG_ABLATION=1)\n", v);
+    warned = true;
+    if (!allow) k.kw3_var = kKw3DefaultVar;
   }
-  int BM, BN;
-  dma_tile_dims(a, a.mask != nullptr, BM, BN);
-  const long long nwg = (long long)((a.M + BM - 1) / BM) * (a.OCpad / BN);
-  const long long cus = num_cus();
-  if (nwg * 2 > cus || nk < 8) return 1;
-  long long k = (cus + nwg - 1) / nwg;  // about one workgroup per CU
-  k = std::min<long long>(k, nk / 4);   // >= 4 K tiles per split keeps the pipeline primed
-  k = std::min<long long>(k, 32);
-  return k < 2 ? 1 : (int)k;
+  k.kw3_tile_512 = is(dv_ab_env("DV_KW3_TILE"), "512x128");
+  k.kw3_sk_all = is(dv_ab_env("DV_KW3_SK"), "all");
+  k.kw3p_epi_reg = is(dv_ab_env("DV_KW3P_EPI"), "reg");
+  k.kw3p_unp_nt = !is(dv_ab_env("DV_KW3P_UNP_NT"), "0");
+  k.no_kw3p_unpool = dv_ab_env("DV_NO_KW3P_UNPOOL") != nullptr;
+  k.kw3p_no_pre = dv_ab_env("DV_KW3P_NO_PRE") != nullptr;
+  return k;
 }
+
+DmaPlan conv_dma_plan(const ConvArgs& a, int amode, int epi) { return dma_plan(a, amode, epi, device_cus(), dma_knobs()); }
 
 // The split-K epilogue: out = act(sum_s ws[s] + bias) with the kernel epilogue's full semantics
 // (16-bit or fp32 output of row stride out_ld): v = sum + bias, [ReLU] (before an accumulate /
@@ -90,32 +98,23 @@ int splitk_reduce_launch(const ConvArgs& a, int epi, hipStream_t s) {
   return (int)hipGetLastError();
 }
 
-int conv_dma_launch(const ConvArgs& a, int amode, int epi, hipStream_t s) {
-  if (a.C % 8 != 0 || a.Kpad % 64 != 0 || a.x_ld % 8 != 0) return -4;
-  if (a.mask != nullptr) {
-    if (a.mask_ld != a.x_ld || epi != CONV_E_BF16) return -4;
-    if (amode == CONV_A_FWD)
-      return a.dtype == DT_F16 ? dma_mask_bn<DT_F16, CONV_A_FWD>(a, s) : dma_mask_bn<DT_BF16, CONV_A_FWD>(a, s);
-    if (amode == CONV_A_TRANSPOSE)
-      return a.dtype == DT_F16 ? dma_mask_bn<DT_F16, CONV_A_TRANSPOSE>(a, s)
-                               : dma_mask_bn<DT_BF16, CONV_A_TRANSPOSE>(a, s);
-    return -1;
-  }
-  if (a.dtype == DT_F16) {  // DeepDream fp16 (BASELINE config 5) + the fp16 deconvnet (Config.dtype)
-    if (amode == CONV_A_FWD && epi == CONV_E_BF16) return dma_run_f16_fwd(a, s);
-    if (amode == CONV_A_FWD && epi == CONV_E_POOL) return dma_run_f16_fwd_pool(a, s);
-    if (amode == CONV_A_FWD && epi == CONV_E_F32) return dma_run_f16_fwd_f32(a, s);
-    if (amode == CONV_A_TRANSPOSE && epi == CONV_E_BF16) return dma_run_f16_tr(a, s);
-    return -1;
-  }
-  if (amode == CONV_A_FWD) {
-    if (epi == CONV_E_BF16) return dma_run_bf16_fwd(a, s);
-    if (epi == CONV_E_POOL) return dma_run_bf16_fwd_pool(a, s);
-    if (epi == CONV_E_F32) return dma_run_bf16_fwd_f32(a, s);
-  } else if (amode == CONV_A_TRANSPOSE) {
-    if (epi == CONV_E_BF16) return dma_run_bf16_tr(a, s);
-  }
-  return -1;
+int conv_dma_run(const ConvArgs& a, const DmaPlan& p, hipStream_t s) {
+  if (p.status != 0) return p.status;
+  const bool f16 = a.dtype == DT_F16, fwd = p.amode == CONV_A_FWD;
+  const int rc = [&] {  // the instantiation units; fp16: DeepDream (BASELINE config 5) and the fp16 deconvnet
+    if (p.mask)
+      return fwd ? (f16 ? dma_run_mask<DT_F16, CONV_A_FWD>(a, p, s) : dma_run_mask<DT_BF16, CONV_A_FWD>(a, p, s))
+                 : (f16 ? dma_run_mask<DT_F16, CONV_A_TRANSPOSE>(a, p, s) : dma_run_mask<DT_BF16, CONV_A_TRANSPOSE>(a, p, s));
+    if (!fwd) return f16 ? dma_run_f16_tr(a, p, s) : dma_run_bf16_tr(a, p, s);
+    if (p.epi == CONV_E_BF16) return f16 ? dma_run_f16_fwd(a, p, s) : dma_run_bf16_fwd(a, p, s);
+    if (p.epi == CONV_E_POOL) return f16 ? dma_run_f16_fwd_pool(a, p, s) : dma_run_bf16_fwd_pool(a, p, s);
+    return f16 ? dma_run_f16_fwd_f32(a, p, s) : dma_run_bf16_fwd_f32(a, p, s);
+  }();
+  if (rc < 0) return rc;  // refused: nothing ran, no route reported
+  const int pre = g_route.flags & (CR_F_UNPOOL | CR_F_RELU_COPY);  // the pre-pass flags bindings.cpp set stay
+  g_route = plan_route(p);
+  g_route.flags |= pre;
+  return rc;
 }
 
 }  // namespace dv

@@ -17,11 +17,13 @@
 //   * STAGES-deep LDS ring, one barrier per K tile: the DMA for tile t+STAGES-1 is issued right
 //     after the barrier of tile t and a counted `s_waitcnt vmcnt(N)` leaves the younger tiles in
 //     flight across the barrier (raw s_barrier, never __syncthreads, so nothing drains them).
-// LDS-DMA implicit-GEMM conv: kernel templates, tile configs and per-problem tile choice.
-// Shared by the instantiation units conv_dma_<dtype>_<mode>.hip (one dma_bn<DT, AMODE, EPI>
-// each, compiled in parallel) and conv_dma.hip (dispatch, split-K, masked dgrads, tuning state).
+// LDS-DMA implicit-GEMM conv: kernel templates and the switch that instantiates them for a planned
+// launch (the routing policy and the tile table are conv_dma_plan.h). Shared by the instantiation units
+// conv_dma_<dtype>_<mode>.hip (one dma_run<DT, AMODE, EPI> each, compiled in parallel) and conv_dma.hip
+// (knobs, plan, dispatch, split-K reduction, masked dgrads, tuning state).
 #pragma once
 #include "common.h"
+#include "conv_dma_plan.h"
 #include "kernels.h"
 
 #include <cstdlib>
@@ -83,17 +85,6 @@ __device__ __forceinline__ int row_xor(int row) {
 }
 
 }  // namespace
-
-// Which pooled-max epilogue a tile can take: shared by conv_dma_body / epilogue (the choice) and dma_cfg (the
-// route report of that choice), so the report cannot drift from the kernel. LDS ring of a tile in bytes; the
-// transposed 8-B stores need 64-row waves; the LDS-staged form also the [BM/4][BN] values + codes in the ring.
-constexpr int dma_ring_bytes(int BM, int BN, int BK, int STAGES, bool MASK) {
-  return STAGES * ((MASK ? 2 : 1) * BM + BN) * BK * 2;
-}
-constexpr bool pool_t_fits(int FM) { return FM % 4 == 0; }
-constexpr bool pool_lds_fits(int FM, int BM, int BN, int ring_bytes) {
-  return pool_t_fits(FM) && BN % 16 == 0 && (BM / 4) * BN * 3 <= ring_bytes;
-}
 
 template <int DT, int FM, int FN, int EPI, bool accum>
 __device__ __forceinline__ void epilogue(const ConvArgs& a, const f32x4 (&acc)[FM][FN], int mw, int nw, int lane);
@@ -968,10 +959,7 @@ __device__ __forceinline__ void epilogue_lds(const ConvArgs& a, const f32x4 (&ac
 // conflict-free ds_read_b128 fragment reads for 16 slots of consecutive indices mod 8 at any base.
 namespace {
 __device__ __forceinline__ int kw3_swz(int row) { return ((row >> 2) & 1) << 1; }
-// staged A slots per workgroup: 8 waves x 16 x A_I >= BM + 2 + 8 x (row boundaries), host-checked
-constexpr int kw3_a_i(int bm) { return bm == 256 ? 4 : 5; }
-constexpr int kKw3Pad = 8;  // zero slots between image rows: a row jump is +9 slots = +1 (mod 8)
-constexpr int kKw3DefaultVar = 2;
+// staged A slots per workgroup: 8 waves x 16 x A_I >= BM + 2 + 8 x (row boundaries), checked by conv_dma_plan.h
 
 // Where issue() finds the B sub-tile (kh, cc, kw, 16-row block rb) of the tile at column n0: byte offset
 // lane + kh s_kh + cc s_cc + n0 s_n0 + kw s_kw + rb s_rb from base. Every term but ``lane`` is wave-uniform
@@ -1687,223 +1675,78 @@ __global__ void __launch_bounds__(512) conv_dma_kw3p_kernel(const ConvArgs a, in
   }
 }
 
-static int num_cus() {
-  static int n = [] {
-    int dev = 0, cu = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cu = 256;
-    return cu > 0 ? cu : 256;
-  }();
-  return n;
-}
+// Tuning override (tools/tune_dma.py, conv_dma.hip:conv_dma_tune): host-side globals, set between launches.
+extern int g_cfg, g_ks;
 
-// DV_KW3: 0 disables the shared-kw-tap kernel (A/B), 2 forces it for every eligible launch regardless
-// of the grid size and ahead of the small-problem tile choice (dma_bn; tests: small shapes with many
-// image borders per tile). Read per launch.
-static int kw3_mode() {
-  const char* e = dv_ab_env("DV_KW3");
-  return e ? std::atoi(e) : 1;
-}
-// DV_KW3_VAR: the KW3 main-loop variant (conv_dma_kw3_kernel VAR; 8 / 9 and 10 (KW3P without stores) are
-// timing ablations that produce wrong outputs; 11 = KW3P with nt stores, tools/kw3_ab.py only: they also need DV_ALLOW_WRONG_ABLATION=1, so a stray
-// DV_KW3_VAR in a serving process cannot corrupt convs; without it they fall back to the default).
-// Read per launch.
-static int kw3_var() {
-  const char* e = dv_ab_env("DV_KW3_VAR");
-  const int v = e ? std::atoi(e) : kKw3DefaultVar;
-  if (v == 8 || v == 9 || v == 10 || v == 20 || v == 21) {
-    static bool warned = false;
-    if (dv_ab_env("DV_ALLOW_WRONG_ABLATION") == nullptr) {
-      if (!warned) fprintf(stderr, "deconv_api_amd: DV_KW3_VAR=%d ignored (needs DV_ALLOW_WRONG_ABLATION=1)\n", v);
-      warned = true;
-      return kKw3DefaultVar;
-    }
-    if (!warned) fprintf(stderr, "deconv_api_amd: DV_KW3_VAR=%d: timing ablation, outputs are WRONG\n", v);
-    warned = true;
-  }
-  return v;
-}
+// The launch half: these functions instantiate the kernels and launch what the plan (conv_dma_plan.h) chose.
+template <int V> using ic = std::integral_constant<int, V>;
 
-// DV_KW3P_NO_PRE=1: KW3P without the step-1 DMA issued ahead of the epilogue stores (A/B; read per launch)
-static int kw3p_pre() { return dv_ab_env("DV_KW3P_NO_PRE") == nullptr ? 1 : 0; }
-
-// KW3P stream-K applies (conv_dma_kw3p_kernel SK): a workspace was passed (bindings.cpp), not switched off
-// (DV_NO_KW3_SK=1, read per launch), one workgroup per CU with the column groups dividing the grid, more
-// tiles than workgroups, and every workgroup's range at least one tile long (at most one split tile at
-// each end of a range). The caller checked the KW3P epilogue conditions.
-static bool kw3_sk_ok(const ConvArgs& a, int BM, int BN) {
-  if (a.skw == nullptr || a.skflag == nullptr || a.m_base != 0 || std::getenv("DV_NO_KW3_SK") != nullptr) return false;
-  if (a.res != nullptr || a.emask != nullptr || a.accumulate || a.out2 != nullptr || a.OC != a.OCpad || a.OC % 8 ||
-      a.out_ld % 8 || a.H >= 4096 || 2LL * a.H * a.W + BM >= (1LL << 19) || a.dtype != DT_BF16 && a.dtype != DT_F16)
-    return false;  // (the KW3P epilogue conditions of kw3_try)
-  if (a.ucode != nullptr ? (a.W < 8 || a.ucode_div < 1) : a.out_elems * 2 >= 0x7FFFFFF0LL) return false;
-  const int G = num_cus(), tiles_n = a.OCpad / BN;
-  const long long tiles_m = (a.M + BM - 1) / BM;
-  // (only short grids: stream-K removes a partial last round, 1.53 rounds on the block5 forward convs,
-  // 0.26 -> 0.22 ms; on many-round grids its split-tile traffic and lost A sharing cost 1-3 %,
-  // profiles/kw3_sk_ab_r5.txt)
-  // (DV_KW3_SK=all: every eligible grid, A/B; read per launch)
-  const char* ska = dv_ab_env("DV_KW3_SK");
-  const long long max_tiles = ska && std::strcmp(ska, "all") == 0 ? (1LL << 40) : 4LL * G;
-  return G <= kSkMaxWg && G <= a.skslots && (long long)BM * BN <= kSkSlotFloats && tiles_n >= 1 && G % tiles_n == 0 &&
-         tiles_m * tiles_n > G && tiles_m * tiles_n < max_tiles && tiles_m >= G / tiles_n &&
-         tiles_m * (3LL * a.C / 32) < (1LL << 31);
-}
-
-// tiles_m_limit > 0: launch only the first tiles_m_limit row tiles (kw3_split's full rounds)
-template <int DT, int AMODE, int EPI, int BN = 256, int BM = 256>
-static int kw3_try(const ConvArgs& a, hipStream_t s, int tiles_m_limit = 0) {
-  if constexpr (AMODE != CONV_A_FWD || EPI == CONV_E_POOL) {
-    return -4;
-  } else {
-    if (kw3_mode() == 0 || a.KH != 3 || a.KW != 3 || a.stride != 1 || a.pad_h != 1 || a.pad_w != 1 || a.H != a.OH ||
-        a.W != a.OW || a.W < 1 || a.C % 32 || a.mask || a.ws || a.OCpad % BN || (long long)a.Kpad < 9LL * a.C)
-      return -4;
-    // zero-padded slots of a BM-row tile: BM + 2 + 8 x (image-row boundaries, <= (BM - 1) / W + 1)
-    if (BM + 2 + kKw3Pad * ((BM - 1) / a.W + 1) > kw3_a_i(BM) * 8 * 16) return -4;  // W >= 9 (256), >= 35 (512)
-    if (a.m_base != 0) return -4;
-    int tiles_m = (a.M + BM - 1) / BM;
-    if (tiles_m_limit > 0 && tiles_m_limit < tiles_m) tiles_m = tiles_m_limit;
-    const int tiles_n = a.OCpad / BN;
-    const long long nwg = (long long)tiles_m * tiles_n;
-    if (nwg <= 0 || nwg > 0x7fffffffLL) return -2;
-    // (a B-fragment double buffer across the kw sub-steps measured equal and was removed,
-    // profiles/layers_r1_kw3_{nofp,on}.txt)
-    const int var = kw3_var();
-    const dim3 grid((unsigned)nwg);
-    if constexpr (EPI == CONV_E_BF16) {
-      // VAR 10 / 11 (bf16 only): KW3P without epilogue stores (timing ablation) / with nt stores
-      const bool pvar = var == 2 || (DT == DT_BF16 && (var == 10 || var == 11 || var == 20 || var == 21));
-      auto launch_p = [&](auto em) -> int {
-        constexpr int U = decltype(em)::value;
-        const unsigned g = (unsigned)(nwg < (long long)num_cus() ? nwg : (long long)num_cus());
-        route_set(CR_KW3P, BM, BN, 0, 0, U == 1 ? CR_E_UNPOOL : (U == 2 ? CR_E_LDS : CR_E_REG));
-        g_route.bpack = a.wp != nullptr;  // B staged from the packed image (bindings.cpp conv_bpack())
-        if constexpr (DT == DT_BF16) {
-          if (var == 10) {
-            hipLaunchKernelGGL((conv_dma_kw3p_kernel<DT, BN, BM, U, 1>), dim3(g), dim3(512), 0, s, a, tiles_n, (int)nwg, kw3p_pre());
-            return (int)hipGetLastError();
-          }
-          if (var == 11) {
-            hipLaunchKernelGGL((conv_dma_kw3p_kernel<DT, BN, BM, U, 2>), dim3(g), dim3(512), 0, s, a, tiles_n, (int)nwg, kw3p_pre());
-            return (int)hipGetLastError();
-          }
-          if (var == 20 || var == 21) {
-            if (var == 20)
-              hipLaunchKernelGGL((conv_dma_kw3p_kernel<DT, BN, BM, U, 3>), dim3(g), dim3(512), 0, s, a, tiles_n, (int)nwg, 0);
-            else
-              hipLaunchKernelGGL((conv_dma_kw3p_kernel<DT, BN, BM, U, 4>), dim3(g), dim3(512), 0, s, a, tiles_n, (int)nwg, 0);
-            return (int)hipGetLastError();
-          }
-        }
-        // the unpool-out epilogue's stores are non-temporal (the 4x-upsampled map, 3/4 zeros, streams past the
-        // caches): config 2 +0.3 % (3 / 3 pairs, profiles/bench_c2_r5_unp_nt_ab.txt). DV_KW3P_UNP_NT=0: plain
-        // stores (A/B; read per launch)
-        if constexpr (U == 1) {
-          const char* unt = dv_ab_env("DV_KW3P_UNP_NT");
-          if (!(unt && std::strcmp(unt, "0") == 0) && !(tiles_m_limit == 0 && kw3_sk_ok(a, BM, BN))) {
-            hipLaunchKernelGGL((conv_dma_kw3p_kernel<DT, BN, BM, U, 2>), dim3(g), dim3(512), 0, s, a, tiles_n, (int)nwg,
-                               kw3p_pre());
-            return (int)hipGetLastError();
-          }
-        }
-        if (tiles_m_limit == 0 && kw3_sk_ok(a, BM, BN)) {  // stream-K over the whole grid (no tail launch)
-          const int G = num_cus();
-          g_route.flags |= CR_F_SK;
-          if (hipMemsetAsync(a.skflag, 0, (size_t)G * sizeof(unsigned), s) != hipSuccess) return (int)hipGetLastError();
-          hipLaunchKernelGGL((conv_dma_kw3p_kernel<DT, BN, BM, U, 0, true>), dim3(G), dim3(512), 0, s, a, tiles_n,
-                             (int)nwg, kw3p_pre());
-          return (int)hipGetLastError();
-        }
-        hipLaunchKernelGGL((conv_dma_kw3p_kernel<DT, BN, BM, U>), dim3(g), dim3(512), 0, s, a, tiles_n, (int)nwg, kw3p_pre());
-        return (int)hipGetLastError();
-      };
-      // persistent KW3P: plain 16-bit epilogue only (its register-transpose stores write exactly
-      // the C tile), output addressable by a 31-bit buffer offset, one workgroup per CU
-      if (pvar && a.res == nullptr && a.emask == nullptr && !a.accumulate && a.ucode == nullptr &&
-          a.out2 == nullptr && a.OC == a.OCpad && a.OC % 4 == 0 && a.out_ld % 4 == 0 &&
-          a.out_elems * 2 < 0x7FFFFFF0LL && a.H < 4096 && 2LL * a.H * a.W + BM < (1LL << 19))
-        // the LDS-sliced 16-B store epilogue unless DV_KW3P_EPI=reg (A/B) or the rows are not 16-B aligned:
-        // config-2 KW3P launches 9-13 % faster than with the register-transposed 8-B stores
-        // (profiles/kw3_epi_ab_r5.txt), config 2 +6.6 % (7418 / 7457 vs 6966 / 6985 img/s, same box)
-        return (dv_ab_env("DV_KW3P_EPI") == nullptr || std::strcmp(dv_ab_env("DV_KW3P_EPI"), "reg") != 0) &&
-                       a.OC % 8 == 0 && a.out_ld % 8 == 0
-                   ? launch_p(std::integral_constant<int, 2>{})
-                   : launch_p(std::integral_constant<int, 0>{});
-      // persistent KW3P with the LDS-sliced max-unpool-out epilogue (DV_NO_KW3P_UNPOOL=1: the
-      // non-persistent KW3 kernel's workgroup-staged one, A/B; read per launch)
-      if (pvar && a.ucode != nullptr && a.res == nullptr && a.emask == nullptr && !a.accumulate &&
-          a.out2 == nullptr && a.OC == a.OCpad && a.OC % 8 == 0 && a.out_ld % 8 == 0 && a.W >= 8 && a.ucode_div >= 1 &&
-          a.H < 4096 && 2LL * a.H * a.W + BM < (1LL << 19) && dv_ab_env("DV_NO_KW3P_UNPOOL") == nullptr)
-        return launch_p(std::integral_constant<int, 1>{});
-    }
-    route_set(CR_KW3, BM, BN, 0, 0, CR_E_NONE);
-    g_route.bpack = a.wp != nullptr;
-    if constexpr (DT == DT_BF16 && EPI == CONV_E_BF16) {
-      if (var == 8 || var == 9) {
-        if (var == 8)
-          hipLaunchKernelGGL((conv_dma_kw3_kernel<DT, EPI, BN, BM, 8>), grid, dim3(512), 0, s, a, tiles_n);
-        else
-          hipLaunchKernelGGL((conv_dma_kw3_kernel<DT, EPI, BN, BM, 9>), grid, dim3(512), 0, s, a, tiles_n);
-        return (int)hipGetLastError();
-      }
-    }
-    hipLaunchKernelGGL((conv_dma_kw3_kernel<DT, EPI, BN, BM, 0>), grid, dim3(512), 0, s, a, tiles_n);
-    return (int)hipGetLastError();
-  }
-}
-
-template <int DT, int WM, int WN, int FM, int FN, int BK, int ST, int AMODE, int EPI, bool MASK = false,
-          bool FP = false>
-static int dma_cfg(const ConvArgs& a, hipStream_t s) {
-  constexpr int BM = WM * FM * 16, BN = WN * FN * 16;
-  constexpr int NT = WM * WN * 64;
-  const int tiles_m = (a.M - a.m_base + BM - 1) / BM;
+// KW3 / KW3P on BM x BN tiles: the first plan.tiles_m_limit row tiles (0: all of them)
+template <int DT, int EPI, int BN, int BM>
+static int kw3_launch(const ConvArgs& a, const DmaPlan& p, hipStream_t s) {
+  int tiles_m = (a.M + BM - 1) / BM;
+  if (p.tiles_m_limit > 0 && p.tiles_m_limit < tiles_m) tiles_m = p.tiles_m_limit;
   const int tiles_n = a.OCpad / BN;
   const long long nwg = (long long)tiles_m * tiles_n;
-  if (nwg <= 0 || nwg > 0x7fffffffLL) return -2;
-  const bool aligned = (a.C % BK) == 0;
-  const dim3 grid((unsigned)nwg, (unsigned)(a.ws ? a.ksplit : 1));
-  int epi_kind = CR_E_NONE;
-  if constexpr (EPI == CONV_E_POOL) {  // the pooled-max epilogue conv_dma_body takes: the kernel's own conditions
-    constexpr bool lds_fits = pool_lds_fits(FM, BM, BN, dma_ring_bytes(BM, BN, BK, ST, MASK));
-    epi_kind = (lds_fits && a.pool_t == 2) ? CR_E_POOL_LDS : ((pool_t_fits(FM) && a.pool_t) ? CR_E_POOL_T : CR_E_POOL);
+  // (a B-fragment double buffer across the kw sub-steps measured equal and was removed,
+  // profiles/layers_r1_kw3_{nofp,on}.txt)
+  if constexpr (EPI == CONV_E_BF16) {
+    // persistent KW3P with epilogue U, one workgroup per CU; store variant SV (1 / 3 / 4: bf16-only timing
+    // ablations, 2: nt stores, the unpool-out epilogue's default)
+    auto launch_p = [&](auto em) -> int {
+      constexpr int U = decltype(em)::value;
+      auto go = [&](auto sv, auto sk, unsigned g) {
+        hipLaunchKernelGGL((conv_dma_kw3p_kernel<DT, BN, BM, U, decltype(sv)::value, decltype(sk)::value>), dim3(g),
+                           dim3(512), 0, s, a, tiles_n, (int)nwg, p.kw3_pre);
+        return (int)hipGetLastError();
+      };
+      const unsigned g = (unsigned)(nwg < (long long)p.cus ? nwg : (long long)p.cus);
+      if constexpr (DT == DT_BF16) {
+        if (p.kw3_var == 1) return go(ic<1>{}, std::false_type{}, g);
+        if (p.kw3_var == 3) return go(ic<3>{}, std::false_type{}, g);
+        if (p.kw3_var == 4) return go(ic<4>{}, std::false_type{}, g);
+      }
+      if constexpr (DT == DT_BF16 || U == 1) {
+        if (p.kw3_var == 2) return go(ic<2>{}, std::false_type{}, g);
+      }
+      if (p.kw3_var != 0) return -4;
+      if (!p.sk) return go(ic<0>{}, std::false_type{}, g);
+      // stream-K over the whole grid: one workgroup per CU, partial tiles through the workspace (never without it)
+      if (a.skw == nullptr || a.skflag == nullptr || a.skslots < p.cus) return -6;
+      if (hipMemsetAsync(a.skflag, 0, (size_t)p.cus * sizeof(unsigned), s) != hipSuccess) return (int)hipGetLastError();
+      return go(ic<0>{}, std::true_type{}, (unsigned)p.cus);
+    };
+    if (p.kernel == DK_KW3P)
+      return p.kw3_epi == CR_E_UNPOOL ? launch_p(ic<1>{}) : (p.kw3_epi == CR_E_LDS ? launch_p(ic<2>{}) : launch_p(ic<0>{}));
   }
-  route_set(CR_DMA, BM, BN, ST, a.ws ? a.ksplit : 1, epi_kind, MASK ? CR_F_MASK : 0);
-  if (aligned)
-    hipLaunchKernelGGL((conv_dma_kernel<DT, WM, WN, FM, FN, BK, ST, AMODE, EPI, true, MASK, FP>), grid,
-                       dim3(NT), 0, s, a, tiles_n);
-  else
-    hipLaunchKernelGGL((conv_dma_kernel<DT, WM, WN, FM, FN, BK, ST, AMODE, EPI, false, MASK, FP>), grid,
-                       dim3(NT), 0, s, a, tiles_n);
-  return (int)hipGetLastError();
+  if (p.kernel != DK_KW3) return -4;
+  auto go = [&](auto var) {
+    hipLaunchKernelGGL((conv_dma_kw3_kernel<DT, EPI, BN, BM, decltype(var)::value>), dim3((unsigned)nwg), dim3(512), 0, s,
+                       a, tiles_n);
+    return (int)hipGetLastError();
+  };
+  if constexpr (DT == DT_BF16 && EPI == CONV_E_BF16) {  // the main-loop timing ablations
+    if (p.kw3_var == 8) return go(ic<8>{});
+    if (p.kw3_var == 9) return go(ic<9>{});
+  }
+  return go(ic<0>{});
 }
 
-// KW3 256 x 256 runs one workgroup per CU (144 KiB of LDS), so a grid of R.f rounds pays a whole
-// round for its fraction f (block5 at B*K = 1024: 1568 tiles = 6.125 rounds; at B = 256: 392 =
-// 1.53). Split: the full rounds as KW3, the last partial round's rows as a tail launch of 128 x 128
-// DMA tiles (4x the workgroups, 2 per CU) starting at row m_base. Same stream, in order.
-template <int DT, int AMODE, int EPI>
-static int kw3_split(const ConvArgs& a, hipStream_t s, long long cus) {
-  if (kw3_sk_ok(a, 256, 256) && kw3_var() == 2) {  // stream-K: no partial round, no tail launch
-    const int rc = kw3_try<DT, AMODE, EPI>(a, s);
-    if (rc != -4) return rc;
-  }
-  const int tiles_m = (a.M + 255) / 256, tiles_n = a.OCpad / 256;
-  const long long nwg = (long long)tiles_m * tiles_n;
-  const long long full = nwg / cus, rem = nwg % cus;
-  const long long main_m = full * cus / tiles_n;  // row tiles of the full rounds
-  if (full < 1 || rem == 0 || (full * cus) % tiles_n != 0 || main_m >= tiles_m)
-    return kw3_try<DT, AMODE, EPI>(a, s);
-  const int rc = kw3_try<DT, AMODE, EPI>(a, s, (int)main_m);
-  if (rc != 0) return rc;  // -4 (unsupported) before anything launched, or a launch error
-  ConvArgs t = a;
-  t.m_base = (int)(main_m * 256);
-  const ConvRoute main_route = g_route;  // the report keeps the main launch, plus the tail flag and its first row
-  const int trc = dma_cfg<DT, 4, 2, 2, 4, 64, 2, AMODE, EPI>(t, s);  // 128 x 128 tail
-  g_route = main_route;
-  g_route.flags |= CR_F_TAIL;
-  g_route.m_base = t.m_base;
-  return trc;
+// the DMA kernel on tile ID of the table (conv_dma_plan.h kDmaTiles), from row a.m_base
+template <int DT, int AMODE, int EPI, int ID>
+static int dma_launch(const ConvArgs& a, hipStream_t s) {
+  constexpr DmaTile T = kDmaTiles[ID];
+  constexpr int BM = T.bm(), BN = T.bn(), NT = T.WM * T.WN * 64;
+  const int tiles_n = a.OCpad / BN;
+  const long long nwg = (long long)((a.M - a.m_base + BM - 1) / BM) * tiles_n;
+  const dim3 grid((unsigned)nwg, (unsigned)(a.ws ? a.ksplit : 1));
+  if (a.C % T.BK == 0)
+    hipLaunchKernelGGL((conv_dma_kernel<DT, T.WM, T.WN, T.FM, T.FN, T.BK, T.ST, AMODE, EPI, true, T.MASK, T.FP>), grid,
+                       dim3(NT), 0, s, a, tiles_n);
+  else
+    hipLaunchKernelGGL((conv_dma_kernel<DT, T.WM, T.WN, T.FM, T.FN, T.BK, T.ST, AMODE, EPI, false, T.MASK, T.FP>), grid,
+                       dim3(NT), 0, s, a, tiles_n);
+  return (int)hipGetLastError();
 }
 
 // Measured and removed (rounds 1-3, profiles/layers_r1_dmav{0,5,6}.txt, layers_r1_ks2_{off,on}.txt,
@@ -1912,170 +1755,46 @@ static int kw3_split(const ConvArgs& a, hipStream_t s, long long cus) {
 // the in-workgroup K split (two wave groups per C tile, partial sums through LDS: the 256x128 /
 // 512x64 tiles are bound by the A-operand DMA stream, not by LDS fragment reads).
 
-// Tuning override (tools/tune_dma.py): force tile config `g_cfg` (> 0) and split-K factor
-// `g_ks` (> 0) for every DMA conv launch until reset to 0. Host-side globals, set between launches.
-extern int g_cfg, g_ks;  // tuning override, defined in conv_dma.hip
-
-// every tile config the DMA kernel is instantiated with; -5 = config does not fit this problem
+// A planned unmasked launch: every unmasked tile of the table, and for forward convs without the pooled
+// epilogue the shared-tap kernels with their 128 x 128 tail.
 template <int DT, int AMODE, int EPI>
-static int dma_forced(const ConvArgs& a, hipStream_t s, int cfg) {
-  auto okn = [&](int bn) { return a.OCpad % bn == 0; };
-  switch (cfg) {
-    case 1: return okn(256) ? dma_cfg<DT, 2, 4, 8, 4, 64, 2, AMODE, EPI, false, true>(a, s) : -5;  // 256x256
-    case 2: return okn(256) ? dma_cfg<DT, 2, 4, 4, 4, 64, 3, AMODE, EPI>(a, s) : -5;               // 128x256
-    case 3: return okn(128) ? dma_cfg<DT, 4, 2, 2, 4, 64, 2, AMODE, EPI>(a, s) : -5;               // 128x128
-    case 4: return okn(128) ? dma_cfg<DT, 4, 2, 4, 4, 64, 3, AMODE, EPI>(a, s) : -5;               // 256x128
-    case 5: return okn(64) ? dma_cfg<DT, 8, 1, 2, 4, 64, 2, AMODE, EPI>(a, s) : -5;                // 256x64
-    case 6: return okn(64) ? dma_cfg<DT, 8, 1, 4, 4, 64, 2, AMODE, EPI>(a, s) : -5;                // 512x64
-    case 7: return okn(64) ? dma_cfg<DT, 4, 1, 2, 4, 64, 3, AMODE, EPI>(a, s) : -5;                // 128x64, 4 waves
-    case 8: return okn(64) ? dma_cfg<DT, 2, 2, 2, 2, 64, 3, AMODE, EPI>(a, s) : -5;                // 64x64, 4 waves
-    case 9: return okn(128) ? dma_cfg<DT, 2, 2, 4, 4, 64, 2, AMODE, EPI>(a, s) : -5;               // 128x128, 4 waves
-    case 10: return okn(128) ? dma_cfg<DT, 2, 2, 2, 4, 64, 3, AMODE, EPI>(a, s) : -5;              // 64x128, 4 waves
-    case 11: return okn(64) ? dma_cfg<DT, 4, 1, 4, 4, 64, 2, AMODE, EPI>(a, s) : -5;               // 256x64, 4 waves
-    // deep rings for latency-bound small GEMMs (more K tiles in flight per workgroup)
-    case 12: return okn(64) ? dma_cfg<DT, 2, 2, 2, 2, 64, 6, AMODE, EPI>(a, s) : -5;               // 64x64 w4 ST6
-    case 13: return okn(64) ? dma_cfg<DT, 2, 2, 2, 2, 64, 8, AMODE, EPI>(a, s) : -5;               // 64x64 w4 ST8
-    case 14: return okn(64) ? dma_cfg<DT, 4, 1, 2, 4, 64, 6, AMODE, EPI>(a, s) : -5;               // 128x64 w4 ST6
-    case 15: return okn(128) ? dma_cfg<DT, 2, 2, 2, 4, 64, 6, AMODE, EPI>(a, s) : -5;              // 64x128 w4 ST6
-    // 8 waves on a 64x64 tile: half the LDS-DMA issues per wave and K tile (the small tiles' K loop
-    // is DMA-issue bound: 4 x ~100 cycles per wave per K tile at 4 waves)
-    case 16: return okn(64) ? dma_cfg<DT, 4, 2, 1, 2, 64, 3, AMODE, EPI>(a, s) : -5;               // 64x64 w8
-    case 17: return okn(64) ? dma_cfg<DT, 4, 2, 1, 2, 64, 4, AMODE, EPI>(a, s) : -5;               // 64x64 w8 ST4
+static int dma_run(const ConvArgs& a, const DmaPlan& p, hipStream_t s) {
+  if constexpr (AMODE == CONV_A_FWD && EPI != CONV_E_POOL) {
+    if (p.kernel != DK_DMA) {
+      const int rc = p.bn == 256 ? kw3_launch<DT, EPI, 256, 256>(a, p, s) : kw3_launch<DT, EPI, 128, 512>(a, p, s);
+      if (rc != 0 || p.m_base == 0) return rc;
+      ConvArgs t = a;  // the last partial round's rows: same stream, in order
+      t.m_base = p.m_base;
+      return dma_launch<DT, AMODE, EPI, kDmaTileTail>(t, s);
+    }
+  }
+  if (p.kernel != DK_DMA) return -4;
+#define DV_TILE(id) case id: return dma_launch<DT, AMODE, EPI, id>(a, s);
+  switch (p.tile) {
+    DV_TILE(1) DV_TILE(2) DV_TILE(3) DV_TILE(4) DV_TILE(5) DV_TILE(6) DV_TILE(7) DV_TILE(8) DV_TILE(9) DV_TILE(10)
+    DV_TILE(11) DV_TILE(12) DV_TILE(13) DV_TILE(14) DV_TILE(15) DV_TILE(16) DV_TILE(17) DV_TILE(18) DV_TILE(19)
     default: return -5;
   }
 }
 
-// Measured override of the size-based choice below for small and narrow-K problems (the DeepDream
-// nets' 1x1 / 1x7 / 5x5 convs and dgrads; tools/tune_dma.py sweep of every launch of configs 3 and 5,
-// profiles/tune_dma_c{3,5}.txt): conv time 9.80 -> 8.52 ms (InceptionV3, 4 octaves) and 6.45 -> 6.07
-// ms (ResNet-50 512^2 x 32). Small problems are bound by per-K-step latency, not MFMA rate: a 64x64
-// 4-wave tile with a 3-stage ring and no split-K; mid-size / short-K ones by the epilogue and DMA
-// issue of one big tile per CU: 128x128. The big-K VGG16 layers keep the large tiles.
-static int auto_cfg(const ConvArgs& a) {
-  static const bool off = dv_ab_env("DV_NO_AUTO_CFG") != nullptr;  // A/B: the size-based choice only
-  if (a.mask != nullptr || off) return 0;
-  const long long mn = (long long)a.M * a.OCpad;
-  // (short K too: M 1600 x N 64 x K 64 4.2 vs 6.0 us for the size-based 256 x 64 tile in a graph,
-  // tools/small_conv_latency.py; DV_SMALL_TILE_KMIN=256 restores the round-1 rule)
-  static const int kmin = dv_ab_env("DV_SMALL_TILE_KMIN") ? std::atoi(dv_ab_env("DV_SMALL_TILE_KMIN")) : 0;
-  // (an 8-wave 64x64 tile with a 4-deep ring, config 17, was -8 % per launch in isolation but
-  // neutral end to end, 417 vs 418 img/s: it stays a tuner-only config)
-  if (a.OCpad % 64 == 0 && a.OC > 16 && mn <= 3000000LL && a.Kpad >= kmin) return 8;
-  if (a.OCpad % 128 == 0 && a.OC > 64 && a.Kpad < 4096 && (a.Kpad < 1024 || mn < 50000000LL)) return 3;
-  return 0;
-}
-
-// Tile choice: the largest tile (best MFMA:LDS ratio) unless it leaves CUs idle. A problem with
-// fewer big tiles than the chip has CUs (deep layers at small batch, strong-scaled tiles) drops to
-// the next smaller tile, which doubles the workgroup count and fits 2 workgroups per CU in LDS.
-template <int DT, int AMODE, int EPI>
-static int dma_bn(const ConvArgs& a, hipStream_t s) {
-  if (g_cfg > 0) return dma_forced<DT, AMODE, EPI>(a, s, g_cfg);
-  // DV_KW3=2 forces the shared-tap kernel ahead of the measured small-problem tiles below too (the tests'
-  // small shapes, K = 9 C < 1024 or few rows, would all take those). Read per launch and only under
-  // DV_ABLATIONS=1 (kw3_mode() is 1 otherwise: a serving process keeps its dispatch whatever its environment holds).
-  if (kw3_mode() == 2) {
-    const int rc = (a.OCpad % 256 == 0 && a.OC > 128) ? kw3_try<DT, AMODE, EPI>(a, s)
-                   : (a.OCpad % 128 == 0 && a.OC > 64) ? kw3_try<DT, AMODE, EPI, 128, 512>(a, s)
-                                                        : -4;
-    if (rc != -4) return rc;
-  }
-  if (const int c = auto_cfg(a)) return dma_forced<DT, AMODE, EPI>(a, s, c);
-  // (the 3-stage BK=64 ring wins slightly on 256x128; 2 stages elsewhere)
-  const long long cus = num_cus();
-  auto nwg = [&](int BM, int BN) { return (long long)((a.M + BM - 1) / BM) * (a.OCpad / BN); };
-  if (a.OCpad % 256 == 0 && a.OC > 128) {
-    {  // DV_KW3_TILE=512x128 (per launch): the 512 x 128 KW3P tile for these shapes too (A/B)
-      const char* kt = dv_ab_env("DV_KW3_TILE");
-      if (kt && std::strcmp(kt, "512x128") == 0) {
-        const int rc = kw3_try<DT, AMODE, EPI, 128, 512>(a, s);
-        if (rc != -4) return rc;
-      }
-    }
-    if (kw3_mode() == 2) {
-      const int rc = kw3_try<DT, AMODE, EPI>(a, s);
-      if (rc != -4) return rc;
-    }
-    if (nwg(256, 256) < cus && nwg(128, 256) >= cus)
-      return dma_cfg<DT, 2, 4, 4, 4, 64, 3, AMODE, EPI>(a, s);  // 128 x 256, 3-stage
-    if (nwg(256, 256) < cus) return dma_cfg<DT, 4, 2, 2, 4, 64, 2, AMODE, EPI>(a, s);  // 128 x 128
-    {  // 3x3 s1 p1 forward: the three kw taps share one staged A tile
-      const int rc = kw3_split<DT, AMODE, EPI>(a, s, cus);
-      if (rc != -4) return rc;
-    }
-    // 256 x 256 with register double-buffered fragments: +3% on the big VGG layers (profiles/)
-    return dma_cfg<DT, 2, 4, 8, 4, 64, 2, AMODE, EPI, false, true>(a, s);
-  }
-  if (a.OCpad % 128 == 0 && a.OC > 64) {
-    if (kw3_mode() == 2 || nwg(512, 128) >= cus) {  // 3x3 s1 p1 forward: shared-kw-tap 512 x 128 tile
-      const int rc = kw3_try<DT, AMODE, EPI, 128, 512>(a, s);
-      if (rc != -4) return rc;
-    }
-    if (nwg(256, 128) < cus) return dma_cfg<DT, 4, 2, 2, 4, 64, 2, AMODE, EPI>(a, s);  // 128 x 128
-    return dma_cfg<DT, 4, 2, 4, 4, 64, 3, AMODE, EPI>(a, s);  // 256 x 128
-  }
-  if (a.OCpad % 64 == 0 && a.OC > 16) {
-    if (nwg(512, 64) < cus) return dma_cfg<DT, 8, 1, 2, 4, 64, 2, AMODE, EPI>(a, s);  // 256 x 64
-    return dma_cfg<DT, 8, 1, 4, 4, 64, 2, AMODE, EPI>(a, s);  // 512 x 64
-  }
-  if (a.OCpad % 16 == 0) {
-    if (nwg(512, 16) < cus) return dma_cfg<DT, 8, 1, 2, 1, 64, 2, AMODE, EPI>(a, s);  // 256 x 16
-    return dma_cfg<DT, 8, 1, 4, 1, 64, 2, AMODE, EPI>(a, s);  // 512 x 16
-  }
-  return -3;
-}
-
-// ReLU-masked dgrad: the mask tile doubles A's LDS footprint, so smaller tiles than dma_bn
-// (<= 128 KiB of LDS per workgroup at 2 stages)
-template <int DT, int AMODE>
-static int dma_mask_bn(const ConvArgs& a, hipStream_t s) {
-  if (a.OCpad % 256 == 0 && a.OC > 128) return dma_cfg<DT, 2, 4, 4, 4, 64, 2, AMODE, CONV_E_BF16, true>(a, s);  // 128x256
-  if (a.OCpad % 128 == 0 && a.OC > 64) return dma_cfg<DT, 4, 2, 2, 4, 64, 2, AMODE, CONV_E_BF16, true>(a, s);   // 128x128
-  if (a.OCpad % 64 == 0 && a.OC > 16) return dma_cfg<DT, 8, 1, 2, 4, 64, 2, AMODE, CONV_E_BF16, true>(a, s);    // 256x64
-  if (a.OCpad % 16 == 0) return dma_cfg<DT, 8, 1, 2, 1, 64, 2, AMODE, CONV_E_BF16, true>(a, s);                // 256x16
-  return -3;
-}
-
-// Tile dims the default selection above picks, for split-K planning.
-static void dma_tile_dims(const ConvArgs& a, bool mask, int& BM, int& BN) {
-  const long long cus = num_cus();
-  auto nwg = [&](int bm, int bn) { return (long long)((a.M + bm - 1) / bm) * (a.OCpad / bn); };
-  BM = 256;
-  BN = 16;
-  if (!mask) {
-    const int c = auto_cfg(a);
-    if (c == 8 || c == 17) { BM = 64; BN = 64; return; }
-    if (c == 3) { BM = 128; BN = 128; return; }
-  }
-  if (mask) {
-    if (a.OCpad % 256 == 0 && a.OC > 128) { BM = 128; BN = 256; }
-    else if (a.OCpad % 128 == 0 && a.OC > 64) { BM = 128; BN = 128; }
-    else if (a.OCpad % 64 == 0 && a.OC > 16) { BM = 256; BN = 64; }
-    return;
-  }
-  if (a.OCpad % 256 == 0 && a.OC > 128) {
-    if (nwg(256, 256) >= cus) { BM = 256; BN = 256; }
-    else if (nwg(128, 256) >= cus) { BM = 128; BN = 256; }
-    else { BM = 128; BN = 128; }
-  } else if (a.OCpad % 128 == 0 && a.OC > 64) {
-    BM = nwg(256, 128) < cus ? 128 : 256;
-    BN = 128;
-  } else if (a.OCpad % 64 == 0 && a.OC > 16) {
-    BM = nwg(512, 64) < cus ? 256 : 512;
-    BN = 64;
-  } else {
-    BM = nwg(512, 16) < cus ? 256 : 512;
+// ReLU-masked dgrad tiles (16-bit epilogue only)
+template <int DT, int AMODE, int EPI = CONV_E_BF16>
+static int dma_run_mask(const ConvArgs& a, const DmaPlan& p, hipStream_t s) {
+  switch (p.tile) {
+    DV_TILE(20) DV_TILE(21) DV_TILE(22) DV_TILE(23)
+    default: return -5;
   }
 }
+#undef DV_TILE
 
-// one dma_bn<DT, AMODE, EPI> per instantiation unit (conv_dma_*.hip)
-int dma_run_bf16_fwd(const ConvArgs& a, hipStream_t s);
-int dma_run_bf16_fwd_pool(const ConvArgs& a, hipStream_t s);
-int dma_run_bf16_fwd_f32(const ConvArgs& a, hipStream_t s);
-int dma_run_bf16_tr(const ConvArgs& a, hipStream_t s);
-int dma_run_f16_fwd(const ConvArgs& a, hipStream_t s);
-int dma_run_f16_fwd_pool(const ConvArgs& a, hipStream_t s);
-int dma_run_f16_fwd_f32(const ConvArgs& a, hipStream_t s);
-int dma_run_f16_tr(const ConvArgs& a, hipStream_t s);
+// one dma_run<DT, AMODE, EPI> per instantiation unit (conv_dma_*.hip)
+int dma_run_bf16_fwd(const ConvArgs& a, const DmaPlan& p, hipStream_t s);
+int dma_run_bf16_fwd_pool(const ConvArgs& a, const DmaPlan& p, hipStream_t s);
+int dma_run_bf16_fwd_f32(const ConvArgs& a, const DmaPlan& p, hipStream_t s);
+int dma_run_bf16_tr(const ConvArgs& a, const DmaPlan& p, hipStream_t s);
+int dma_run_f16_fwd(const ConvArgs& a, const DmaPlan& p, hipStream_t s);
+int dma_run_f16_fwd_pool(const ConvArgs& a, const DmaPlan& p, hipStream_t s);
+int dma_run_f16_fwd_f32(const ConvArgs& a, const DmaPlan& p, hipStream_t s);
+int dma_run_f16_tr(const ConvArgs& a, const DmaPlan& p, hipStream_t s);
 
 }  // namespace dv

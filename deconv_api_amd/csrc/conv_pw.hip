@@ -130,7 +130,7 @@ int conv_pw_launch(const ConvArgs& a, hipStream_t s) {
       a.C % 64 != 0 || a.Kpad != a.C || a.K != a.C || a.mask || a.code || a.ucode || a.ws || a.stats ||
       a.relu_in || !a.vec_epi || a.x_ld % 8 != 0 || (long long)a.M * a.x_ld * 2 > 0x7FFFFFF0LL)
     return -4;
-  const long long cus = num_cus();
+  const long long cus = device_cus();
   int BM, BN;
   if (a.OCpad % 128 == 0 && a.OC > 64) {
     BM = 128;

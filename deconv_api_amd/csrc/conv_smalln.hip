@@ -1064,13 +1064,7 @@ template <int FN, int EPI, bool UNPOOL>
 static int persist_cfg(const ConvArgs& a, hipStream_t s) {
   const long long ntiles = (long long)a.N * ((a.H + TH - 1) / TH) * ((a.W + TW - 1) / TW);
   if (ntiles <= 0 || ntiles > 0x7fffffffLL) return -2;
-  // CU count queried once (keeps the launch path free of runtime queries during graph capture)
-  static const int cus = [] {
-    int dev = 0, n = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      n = 256;
-    return n > 0 ? n : 256;
-  }();
+  const int cus = device_cus();
   const long long grid = std::min<long long>(ntiles, (long long)cus);
   route_set(CR_HALO_V1, 0, 0, 0, 0, CR_E_PERSIST);
   hipLaunchKernelGGL((conv3x3_c64_persist_kernel<FN, EPI, UNPOOL>), dim3((unsigned)grid), dim3(512), 0, s, a);
@@ -1083,12 +1077,7 @@ int conv3x3_pool_v3_launch(const ConvArgs& a, hipStream_t s) {
       a.Kpad < KW9 || a.x_ld % 8 || a.out_ld % 8 || a.dtype != DT_BF16 || a.res || a.emask ||
       (reinterpret_cast<uintptr_t>(a.out) & 15) || (reinterpret_cast<uintptr_t>(a.out_code) & 15))
     return -4;
-  static const int cus = [] {
-    int dev = 0, n = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      n = 256;
-    return n > 0 ? n : 256;
-  }();
+  const int cus = device_cus();
   const long long ntiles = (long long)a.N * ((a.H + TH - 1) / TH) * ((a.W + TW - 1) / TW);
   if (ntiles <= 0 || ntiles > 0x7fffffffLL) return -2;
   route_set(CR_POOL_V3, 0, 0, 0, 0, CR_E_NONE);
@@ -1105,12 +1094,7 @@ int conv3x3_halo_launch(const ConvArgs& a, int unpool, int epi, hipStream_t s, b
   // v2: unpool + 64 -> 64 with a 16-B aligned bf16 output of 64-channel rows (block1_conv2.down)
   if (unpool && !narrow && epi == CONV_E_BF16 && a.OC == 64 && a.out_ld % 8 == 0 && a.x_ld % 8 == 0 &&
       (a.H % 2) == 0 && (a.W % 2) == 0) {
-    static const int cus = [] {
-      int dev = 0, n = 256;
-      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        n = 256;
-      return n > 0 ? n : 256;
-    }();
+    const int cus = device_cus();
     const long long ntiles = (long long)a.N * ((a.H + TH - 1) / TH) * ((a.W + TW - 1) / TW);
     if (ntiles <= 0 || ntiles > 0x7fffffffLL) return -2;
     route_set(CR_HALO_V2, 0, 0, 0, 0, CR_E_NONE);
@@ -1165,12 +1149,7 @@ int conv3x3_unpool_z_launch(const ConvArgs& a, hipStream_t s) {
       (reinterpret_cast<uintptr_t>(a.out) & 15) || (reinterpret_cast<uintptr_t>(a.w2) & 15) ||
       (reinterpret_cast<uintptr_t>(a.x) & 15) || (reinterpret_cast<uintptr_t>(a.code) & 7))
     return -4;
-  static const int cus = [] {
-    int dev = 0, n = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      n = 256;
-    return n > 0 ? n : 256;
-  }();
+  const int cus = device_cus();
   const long long ntiles = (long long)a.N * ((a.H + TH - 1) / TH) * ((a.W + TW - 1) / TW);
   if (ntiles <= 0 || ntiles > 0x7fffffffLL) return -2;
   // DV_TAIL_V: variant bits (see the kernel); 3 by default, 0 = the round-4 schedule (A/B)

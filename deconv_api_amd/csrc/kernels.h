@@ -4,7 +4,9 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
+#include <cstdio>
 #include <cstdlib>
+#include <string>
 
 // Runtime A/B switch of a measured alternative (deconv_api_amd/knobs.py ABLATION): the variable is read
 // only when DV_ABLATIONS=1, so a serving / benchmark process takes one dispatch per shape whatever its
@@ -51,7 +53,7 @@ struct ConvArgs {
   int K, Kpad;
   int M;                  // GEMM rows = N*OH*OW
   int m_base;             // LDS-DMA / KW3 launches: first GEMM row of tile 0 (a tail launch after a
-                          //   full-round one, conv_dma_impl.h:kw3_split); 0 otherwise
+                          //   full-round one, conv_dma_plan.h:kw3_split); 0 otherwise
   int relu, relu_in, accumulate;
   int dtype;              // 16-bit storage dtype of x/w/mask/16-bit out: 0 bf16, 1 fp16
   const uint16_t* res;    // optional residual (LDS-DMA FWD, 16-bit out): out = [ReLU](acc + bias + res)
@@ -133,7 +135,7 @@ enum ConvRouteFlag : int {
   CR_F_TAIL = 4,      // KW3 / KW3P full rounds + a 128 x 128 DMA tail launch from row m_base
   CR_F_UNPOOL = 8,    // pre-pass: the unpooled input was materialized (unpool2x2)
   CR_F_RELU_COPY = 16,  // pre-pass: dense ReLU copy of the input
-  CR_F_MASK = 32,     // ReLU-masked A operand (dma_mask_bn)
+  CR_F_MASK = 32,     // ReLU-masked A operand (the masked DMA tiles)
 };
 struct ConvRoute {
   int kind, bm, bn, stages, ksplit, epi, flags, m_base, cfg;
@@ -146,22 +148,65 @@ static inline void route_set(int kind, int bm, int bn, int stages, int ksplit, i
   g_route = ConvRoute{kind, bm, bn, stages, ksplit, epi, (g_route.flags & (CR_F_UNPOOL | CR_F_RELU_COPY)) | flags, 0, 0};
 }
 
+// The route as text, e.g. "dma 128x128 st2 ks1", "kw3p 256x256 lds sk", "kw3 256x256 + dma 128x128 tail
+// m_base=65536", "unpool2x2 > dma 64x64 st3 ks1", "group cfg8"; "none": no launch recorded.
+static inline std::string route_str(const ConvRoute& r) {
+  static const char* const kEpi[] = {"", " reg", " lds", " unpool", " pool", " strips", " persist", " pool_t", " pool_lds"};
+  const char* epi = (r.epi >= 0 && r.epi <= 8) ? kEpi[r.epi] : "";
+  char b[160];
+  switch (r.kind) {
+    case CR_IGEMM: std::snprintf(b, sizeof b, "igemm %dx%d", r.bm, r.bn); break;
+    case CR_HALO_V1: std::snprintf(b, sizeof b, "halo_v1%s", epi); break;
+    case CR_HALO_V2: std::snprintf(b, sizeof b, "halo_v2"); break;
+    case CR_POOL_V3: std::snprintf(b, sizeof b, "pool_v3"); break;
+    case CR_C8_STREAM: std::snprintf(b, sizeof b, "c8_stream"); break;
+    case CR_HS16:
+    case CR_HS32:
+      std::snprintf(b, sizeof b, "%s oc%d%s%s%s", r.kind == CR_HS16 ? "hs16" : "hs32", r.bn, epi,
+                    (r.flags & CR_F_OCSPLIT) ? " ocsplit" : "", r.cfg == 1 ? " stem" : "");
+      break;
+    case CR_PW: std::snprintf(b, sizeof b, "pw %dx%d", r.bm, r.bn); break;
+    case CR_DMA:
+      std::snprintf(b, sizeof b, "dma %dx%d st%d ks%d%s%s", r.bm, r.bn, r.stages, r.ksplit, epi,
+                    (r.flags & CR_F_MASK) ? " mask" : "");
+      break;
+    case CR_KW3:
+    case CR_KW3P: {
+      int n = std::snprintf(b, sizeof b, "%s %dx%d%s%s", r.kind == CR_KW3 ? "kw3" : "kw3p", r.bm, r.bn, epi,
+                            (r.flags & CR_F_SK) ? " sk" : "");
+      if ((r.flags & CR_F_TAIL) && n > 0 && n < (int)sizeof b)
+        std::snprintf(b + n, sizeof b - n, " + dma 128x128 tail m_base=%d", r.m_base);
+      break;
+    }
+    case CR_GROUP: std::snprintf(b, sizeof b, "group cfg%d", r.cfg); break;
+    default: std::snprintf(b, sizeof b, "none"); break;
+  }
+  std::string out;
+  if (r.flags & CR_F_UNPOOL) out += "unpool2x2 > ";
+  if (r.flags & CR_F_RELU_COPY) out += "relu_copy > ";
+  return out + b;
+}
+
 // The same for the multi-kernel launchers of misc.hip (seed_deconv3x3, maxpool2x2, unpool2x2) and for
 // bindings.cpp:deprocess_mosaic: the name of the kernel (pair) the last such call on this thread chose
 // (bindings.cpp misc_route()). One pointer store to a string literal on the launch path.
 extern __thread const char* g_misc_route;  // defined in misc.hip
 
 int conv_igemm_launch(const ConvArgs& a, int amode, int epi, hipStream_t stream);
-// LDS-DMA variant (FWD / TRANSPOSE, no mask): 8-wave 128x64-per-wave tiles
-int conv_dma_launch(const ConvArgs& a, int amode, int epi, hipStream_t stream);
-// split-K planning (1 = none) and the reduction epilogue (bias, ReLU, 16-bit / fp32 out)
-int conv_dma_splitk(const ConvArgs& a);
-// tuning override: force DMA tile config cfg (> 0, conv_dma.hip:dma_forced) and split-K ks (> 0); 0 = auto
+// compute units of the current device, cached per device (bindings.cpp): the one source of the CU count. Per call
+// only hipGetDevice, a host-side query that is legal during stream capture; the attribute is read once per device.
+int device_cus();
+// LDS-DMA family (FWD / TRANSPOSE, optionally ReLU-masked): the plan of a launch (conv_dma_plan.h) under the process's
+// knobs on the current device, and the launch of a plan (< 0 when it declines: DmaPlan::status). The caller supplies the
+// workspaces the plan asks for (ws / ksplit for plan.ksplit > 1, skw / skflag / skslots for plan.sk) and reduces.
+struct DmaPlan;
+DmaPlan conv_dma_plan(const ConvArgs& a, int amode, int epi);
+int conv_dma_run(const ConvArgs& a, const DmaPlan& plan, hipStream_t stream);
+// tuning override: force DMA tile config cfg (> 0, conv_dma_plan.h:kDmaTiles 1..17) and split-K ks (> 0); 0 = auto
 void conv_dma_tune(int cfg, int ks);
+// the split-K reduction epilogue (bias, ReLU, accumulate, residual, emask; 16-bit / fp32 out)
 int splitk_reduce_launch(const ConvArgs& a, int epi, hipStream_t stream);
-// tile config a grouped launch of ``a`` would use (conv_dma.hip), 0 = not groupable; and the launch
-// of 1..kGroupMax problems that share it (same dtype, A mode, epilogue and config; no split-K)
-int conv_dma_group_cfg(const ConvArgs& a, int amode, int epi);
+// launch of 1..kGroupMax problems that share a group config (plan.group_cfg != 0), dtype, A mode and epilogue
 int conv_dma_group_launch(const ConvArgs* ps, int n, int amode, int epi, hipStream_t stream);
 // direct VALU kernels for InceptionV3's conv2d_1 (8-ch padded RGB -> 32, 3x3 / stride 2): forward and
 // input gradient (conv_stem.hip); < 0: unsupported geometry
@@ -172,7 +217,7 @@ int stem_conv_dgrad_launch(const uint16_t* gy, const float* w, uint16_t* gx, int
                            int C, int cr, int cout, int k, int stride, int pad, long long gy_ld, long long gx_ld,
                            int dtype, hipStream_t s);
 // persistent pointwise (1x1 / s1 / p0) conv at large M, 16-bit LDS-staged epilogue (conv_pw.hip);
-// < 0: unsupported shape / mode (use conv_dma_launch)
+// < 0: unsupported shape / mode (use conv_dma_run)
 int conv_pw_launch(const ConvArgs& a, hipStream_t stream);
 
 // ---- misc kernels (misc.hip) ----

@@ -190,7 +190,7 @@ def test_exact_kw3_tail_split(native_lib, monkeypatch):
 # LDS-DMA tile matrix
 # ----------------------------------------------------------------------------------------
 
-# tile config (csrc/conv_dma_impl.h dma_forced) -> (BM, BN, stages)
+# tile config (csrc/conv_dma_plan.h kDmaTiles) -> (BM, BN, stages)
 DMA_CFGS = {1: (256, 256, 2), 2: (128, 256, 3), 3: (128, 128, 2), 4: (256, 128, 3), 5: (256, 64, 2), 6: (512, 64, 2),
             7: (128, 64, 3), 8: (64, 64, 3), 9: (128, 128, 2), 10: (64, 128, 3), 11: (256, 64, 2), 12: (64, 64, 6),
             13: (64, 64, 8), 14: (128, 64, 6), 15: (64, 128, 6), 16: (64, 64, 3), 17: (64, 64, 4)}

@@ -815,7 +815,7 @@ def test_conditions():
         assert G < _pool_v3_n(G) * 60 < 2 * G
         for OC in (64, 128, 192, 256):
             _pw_m(G, OC)
-    # cfg 3 groups: M OCpad > 3e6 and Kpad < 1024 (csrc/conv_dma_impl.h auto_cfg)
+    # cfg 3 groups: M OCpad > 3e6 and Kpad < 1024 (csrc/conv_dma_plan.h auto_cfg)
     for p in GROUPS["cfg3"][1]:
         kh, kw_ = p.get("k", (3, 3))
         assert p["N"] * p["H"] * p["W"] * Cm.oc_pad(p["OC"]) > 3_000_000 and kh * kw_ * p["C"] < 1024

@@ -2,7 +2,7 @@
 DeepDream step (or any engine step) and report the automatic choice against the best one.
 
 Each conv2d call of the step is intercepted while its inputs are live and re-run under every
-forced (tile config, split-K) pair (``_C.dma_tune``; configs in csrc/conv_dma.hip:dma_forced),
+forced (tile config, split-K) pair (``_C.dma_tune``; configs 1..17 of csrc/conv_dma_plan.h:kDmaTiles),
 timed over ``--reps`` back-to-back launches with HIP events. Usage (GPU box):
 
     python tools/tune_dma.py --model inception_v3 --batch 64 --size 299 --octaves 4
