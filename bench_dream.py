@@ -49,6 +49,8 @@ def main(argv=None):
     ap.add_argument("--xgmi-gbs", type=float, default=300.0,
                     help="--virtual-world: assumed all-gather receive bandwidth per GPU (GB/s) for the exposed-"
                          "communication estimate (8 x MI355X RCCL all-gather over xGMI; not measured here)")
+    ap.add_argument("--lap-levels", type=int, default=0,
+                    help="untiled only: Laplacian-pyramid gradient normalisation over this many levels (0 = off)")
     a = ap.parse_args(argv)
     if a.virtual_world:
         return virtual_rank(a)
@@ -67,6 +69,7 @@ def main(argv=None):
 
         net = ResNet50(0).build(dev, dt)
         s = DreamSettings(layers=dict(RESNET_LAYERS), octaves=a.octaves, iterations=a.steps)
+    s.lap_levels = a.lap_levels
     if a.tile:
         dd = TiledDeepDream(net, s, tile=a.tile, info=info, use_graphs=not a.no_graphs)
     else:
@@ -100,6 +103,7 @@ def main(argv=None):
             "finite": bool(torch.isfinite(out).all()),
             "sub_batch_streams": dd.split if dd.fused else 1,
             **(_tile_info(dd) if a.tile else {}),
+            **({"lap_levels": a.lap_levels} if a.lap_levels else {}),
             "config": {"model": a.model, "batch": a.batch, "image_size": a.size, "tile": a.tile,
                        "parallelism": f"{'tiles' if a.tile else 'dp'}{info.world}"},
         }), flush=True)

@@ -168,7 +168,9 @@ def create_app(service=None, cfg: Optional[Config] = None, dream_service=None) -
     async def deepdream(request: Request):
         """Extension (not in the reference): DeepDream of the uploaded image. Form fields: file,
         optional model (inception_v3 | resnet50), octaves, steps, guide (a second image, same data-URL
-        conventions as file: the dream is pulled towards its features). Same data-URL conventions."""
+        conventions as file: the dream is pulled towards its features), lap_levels (0..5, default 0: levels of
+        the Laplacian-pyramid gradient normalisation, smoother large-structured dreams). Same data-URL
+        conventions."""
         t0 = time.perf_counter()
         status = "200"
         try:
@@ -179,6 +181,9 @@ def create_app(service=None, cfg: Optional[Config] = None, dream_service=None) -
                     return _missing(["file"])
                 model = form.get("model", "inception_v3")
                 octaves, steps = int(form.get("octaves", 4)), int(form.get("steps", 20))
+                lap = int(form.get("lap_levels", 0))
+                if not 0 <= lap <= 5:
+                    raise ValueError("lap_levels must be 0..5")
             except (FormError, ValueError, LookupError) as e:  # bad body / charset / non-numeric field
                 status = "400"
                 return JSONResponse(status_code=400, content={"detail": str(e)})
@@ -188,10 +193,12 @@ def create_app(service=None, cfg: Optional[Config] = None, dream_service=None) -
 
                 ds = state["dream"] = DreamService(cfg)
             try:
+                kw = {}  # only what the request sets: a plain request is the four-argument call it always was
                 if form.get("guide"):
-                    url = await ds.dream(form["file"], model, octaves, steps, guide=form["guide"])
-                else:
-                    url = await ds.dream(form["file"], model, octaves, steps)
+                    kw["guide"] = form["guide"]
+                if lap:
+                    kw["lap_levels"] = lap
+                url = await ds.dream(form["file"], model, octaves, steps, **kw)
             except (ImageDecodeError, ValueError) as e:
                 status = "400"
                 return JSONResponse(status_code=400, content={"detail": str(e)})

@@ -2,13 +2,14 @@
 
     python -m deconv_api_amd.cli deconv photo.jpg [more.png ...] --layer block5_conv3 [--out-dir out/]
     python -m deconv_api_amd.cli dream photo.jpg --model inception_v3 --octaves 4 --steps 20 [--out-dir out/]
-                                       [--guide other.jpg]
+                                       [--guide other.jpg] [--lap-levels 4]
     python -m deconv_api_amd.cli layers
 
 ``deconv`` writes ``<stem>_<layer>.jpg``: the 2x2 mosaic of the top-4 deconvnet reconstructions, the same
 image ``POST /`` returns as a data URL (reference: app/main.py:45-78), all files as one batch on the device.
 ``dream`` writes ``<stem>_dream_<model>.jpg`` (``POST /deepdream``); with ``--guide`` every image dreams towards
-that image's features (the route's ``guide`` field). Configuration as the server's
+that image's features (the route's ``guide`` field), with ``--lap-levels N`` the gradient of every step is
+Laplacian-pyramid normalised over N levels (the route's ``lap_levels`` field). Configuration as the server's
 (``DV_*`` variables, config.py) with ``--device`` / ``--dtype`` / ``--weights`` overrides.
 """
 from __future__ import annotations
@@ -73,7 +74,8 @@ def cmd_dream(a, cfg) -> int:
     ds = DreamService(cfg)
     try:
         guides = [ds.prepare_guide(_read([a.guide])[0])] if a.guide else None
-        outs = [ds.run_batch([ds.prepare(img, a.octaves)], a.model, a.octaves, a.steps, guides)[0] for img in imgs]
+        kw = {"lap_levels": a.lap_levels} if a.lap_levels else {}
+        outs = [ds.run_batch([ds.prepare(img, a.octaves)], a.model, a.octaves, a.steps, guides, **kw)[0] for img in imgs]
     finally:
         ds.close()
     os.makedirs(a.out_dir, exist_ok=True)
@@ -111,6 +113,8 @@ def main(argv=None) -> int:
     r.add_argument("--octaves", type=int, default=4)
     r.add_argument("--steps", type=int, default=20)
     r.add_argument("--guide", default=None, help="dream towards this image's features (guided DeepDream)")
+    r.add_argument("--lap-levels", type=int, default=0, choices=range(6), metavar="N",
+                   help="Laplacian-pyramid gradient normalisation over N levels (0..5, 0 = off)")
     r.add_argument("--out-dir", default=".")
     sub.add_parser("layers", help="the VGG16 layer names POST / accepts")
     a = ap.parse_args(argv)

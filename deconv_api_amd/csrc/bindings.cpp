@@ -818,6 +818,127 @@ void guide_match(Tensor a, Tensor y, Tensor gidx, Tensor scale, c10::optional<Te
            "guide_match");
 }
 
+// Laplacian-pyramid gradient normalisation (dream_lap.hip). Level l of an [N,H,W,*] map has sides (H_l, W_l), H_0 = H,
+// H_{l+1} = ceil(H_l / 2). Buffers, n = hi.size() levels (1..5), all fp32 contiguous on x's device: hi[l] [N,H_l,W_l,3],
+// lo[l] [N,H_{l+1},W_{l+1},3] (= down of level l), hpart[l] [N, tiles of level l], lpart [N, tiles of level n-1].
+static int lap_layout(const Tensor& t, const char* what) {
+  check_cuda(t, what);
+  TORCH_CHECK(t.dim() == 4 && t.is_contiguous() && t.numel() > 0 && reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+              what, ": contiguous, 16-B aligned [N,H,W,C]");
+  if (t.scalar_type() == at::kFloat) {
+    TORCH_CHECK(t.size(3) == 3, what, ": fp32 needs [N,H,W,3]");
+    return dv::LAP_F32;
+  }
+  TORCH_CHECK(is16(t) && t.size(3) == 8, what, ": fp32 [N,H,W,3] or bf16 / fp16 [N,H,W,8]");
+  return dt_of(t);
+}
+
+static void lap_f3(const Tensor& t, const Tensor& like, int64_t H, int64_t W, const char* what) {
+  check_cuda(t, what);
+  TORCH_CHECK(t.scalar_type() == at::kFloat && t.is_contiguous() && t.dim() == 4 && t.size(0) == like.size(0) &&
+                  t.size(1) == H && t.size(2) == W && t.size(3) == 3 && t.device() == like.device(),
+              what, ": fp32 contiguous [", like.size(0), ", ", H, ", ", W, ", 3] expected, got ", t.sizes());
+}
+
+static void lap_part(const Tensor& t, const Tensor& like, int64_t H, int64_t W, const char* what) {
+  check_cuda(t, what);
+  const int64_t parts = (int64_t)dv::lap_tiles((int)H) * dv::lap_tiles_w((int)W);
+  TORCH_CHECK(t.scalar_type() == at::kFloat && t.is_contiguous() && t.dim() == 2 && t.size(0) == like.size(0) &&
+                  t.size(1) == parts && t.device() == like.device(),
+              what, ": fp32 contiguous [", like.size(0), ", ", parts, "] expected, got ", t.sizes());
+}
+
+// partials per image of an H x W level (one per kernel tile): what the caller allocates
+int64_t lap_parts(int64_t H, int64_t W) {
+  TORCH_CHECK(H >= 1 && W >= 1 && H <= 0x7FFFFFFF && W <= 0x7FFFFFFF, "lap_parts: H, W >= 1");
+  return (int64_t)dv::lap_tiles((int)H) * dv::lap_tiles_w((int)W);
+}
+
+static void lap_levels_ok(const Tensor& x, size_t n) {
+  TORCH_CHECK(n >= 1 && n <= (size_t)dv::LAP_MAX_LEVELS, "lap: 1 <= levels <= 5, got ", n);
+  TORCH_CHECK(x.size(0) <= 65535 && x.size(1) * x.size(2) * 8 <= 0x7FFFFFFFLL, "lap: map too large");
+}
+
+void lap_split(Tensor x, std::vector<Tensor> lo, std::vector<Tensor> hi, std::vector<Tensor> hpart, Tensor lpart) {
+  const int src = lap_layout(x, "lap_split: x");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  const size_t n = hi.size();
+  lap_levels_ok(x, n);
+  TORCH_CHECK(lo.size() == n && hpart.size() == n, "lap_split: lo, hi, hpart of one length");
+  int64_t H = x.size(1), W = x.size(2);
+  for (size_t l = 0; l < n; ++l, H = (H + 1) / 2, W = (W + 1) / 2) {
+    lap_f3(hi[l], x, H, W, "lap_split: hi");
+    lap_f3(lo[l], x, (H + 1) / 2, (W + 1) / 2, "lap_split: lo");
+    lap_part(hpart[l], x, H, W, "lap_split: hpart");
+    if (l + 1 == n) lap_part(lpart, x, H, W, "lap_split: lpart");
+  }
+  H = x.size(1), W = x.size(2);
+  for (size_t l = 0; l < n; ++l, H = (H + 1) / 2, W = (W + 1) / 2)
+    check_rc(dv::lap_split_launch(l == 0 ? x.data_ptr() : (const void*)lo[l - 1].data_ptr<float>(),
+                                  l == 0 ? src : dv::LAP_F32, lo[l].data_ptr<float>(), hi[l].data_ptr<float>(),
+                                  hpart[l].data_ptr<float>(), l + 1 == n ? lpart.data_ptr<float>() : nullptr,
+                                  (int)x.size(0), (int)H, (int)W, cur_stream()),
+             "lap_split");
+}
+
+// out = merge([lo[n-1], hi[n-1], ..., hi[0]], s): merged[l-1] [N,H_l,W_l,3] (l = 1..n-1) hold the intermediate
+// images, out is fp32 [N,H,W,3] or 16-bit [N,H,W,8]. s: ``scales`` fp32 [N, n+1] in that order (column 0: the
+// coarsest lo), or - scales absent - 1 / max(rms, eps) from the partials of lap_split.
+void lap_merge(Tensor lo_n, std::vector<Tensor> hi, std::vector<Tensor> merged, Tensor out,
+               c10::optional<Tensor> scales, std::vector<Tensor> hpart, c10::optional<Tensor> lpart, double eps) {
+  const int dst = lap_layout(out, "lap_merge: out");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(out.device());
+  const size_t n = hi.size();
+  lap_levels_ok(out, n);
+  TORCH_CHECK(merged.size() + 1 == n, "lap_merge: one merged buffer per level 1..n-1");
+  std::vector<int64_t> Hs{out.size(1)}, Ws{out.size(2)};
+  for (size_t l = 0; l < n; ++l) {
+    Hs.push_back((Hs[l] + 1) / 2);
+    Ws.push_back((Ws[l] + 1) / 2);
+  }
+  for (size_t l = 0; l < n; ++l) {
+    lap_f3(hi[l], out, Hs[l], Ws[l], "lap_merge: hi");
+    if (l > 0) lap_f3(merged[l - 1], out, Hs[l], Ws[l], "lap_merge: merged");
+  }
+  lap_f3(lo_n, out, Hs[n], Ws[n], "lap_merge: lo");
+  const float* sp = nullptr;
+  if (scales.has_value()) {
+    check_cuda(*scales, "lap_merge: scales");
+    TORCH_CHECK(scales->scalar_type() == at::kFloat && scales->is_contiguous() && scales->dim() == 2 &&
+                    scales->size(0) == out.size(0) && scales->size(1) == (int64_t)n + 1 &&
+                    scales->device() == out.device(),
+                "lap_merge: scales fp32 contiguous [N, levels + 1]");
+    sp = scales->data_ptr<float>();
+  } else {
+    TORCH_CHECK(hpart.size() == n && lpart.has_value(), "lap_merge: scales or the partials of lap_split");
+    TORCH_CHECK(eps > 0, "lap_merge: eps > 0");
+    for (size_t l = 0; l < n; ++l) lap_part(hpart[l], out, Hs[l], Ws[l], "lap_merge: hpart");
+    lap_part(*lpart, out, Hs[n - 1], Ws[n - 1], "lap_merge: lpart");
+  }
+  for (size_t l = n; l-- > 0;) {
+    const bool first = l + 1 == n;
+    const float* prev = first ? lo_n.data_ptr<float>() : merged[l].data_ptr<float>();
+    void* o = l == 0 ? out.data_ptr() : (void*)merged[l - 1].data_ptr<float>();
+    check_rc(dv::lap_merge_launch(prev, hi[l].data_ptr<float>(), o, l == 0 ? dst : dv::LAP_F32, sp, (int)n + 1,
+                                  (int)(n - l), sp ? nullptr : hpart[l].data_ptr<float>(),
+                                  sp ? 0 : (int)hpart[l].size(1), sp || !first ? nullptr : lpart->data_ptr<float>(),
+                                  sp || !first ? 0 : (int)lpart->size(1), (float)eps, first ? 1 : 0, (int)out.size(0),
+                                  (int)Hs[l], (int)Ws[l], cur_stream()),
+             "lap_merge");
+  }
+}
+
+// out = lap_normalize(g): lap_split then lap_merge with the scales from the partials (2n launches)
+void lap_normalize(Tensor g, std::vector<Tensor> lo, std::vector<Tensor> hi, std::vector<Tensor> hpart, Tensor lpart,
+                   std::vector<Tensor> merged, Tensor out, double eps) {
+  TORCH_CHECK(!lo.empty() && lo.size() == hi.size(), "lap_normalize: lo, hi of one length >= 1");
+  TORCH_CHECK(out.dim() == 4 && g.dim() == 4 && out.size(0) == g.size(0) && out.size(1) == g.size(1) &&
+                  out.size(2) == g.size(2) && out.device() == g.device(),
+              "lap_normalize: out of g's N, H, W and device");
+  lap_split(g, lo, hi, hpart, lpart);
+  lap_merge(lo.back(), hi, merged, out, c10::nullopt, hpart, lpart, eps);
+}
+
 // Fused DeepDream update (engine/deepdream.py): g [N,H,W,8] 16-bit input gradient, x [N,H,W,3] fp32
 // master image (updated in place), xin [N,H,W,8] next network input, gpart [N, P] scratch, lpart
 // [L, N, LP] sumsq partials of the L loss layers, lcoef [L] fp32 coefficient / numel, done u8 [N],
@@ -1675,6 +1796,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("world"), py::arg("k0") = 0);
   m.def("tile_update", &tile_update, "tiled DeepDream: normalize + update the image from every rank's packs");
   m.def("tile_pack_elems", &tile_pack_elems);
+  m.def("lap_split", &lap_split, "Laplacian pyramid split: lo / hi levels + sum-of-squares partials", py::arg("x"),
+        py::arg("lo"), py::arg("hi"), py::arg("hpart"), py::arg("lpart"));
+  m.def("lap_parts", &lap_parts, "partials per image of an H x W pyramid level", py::arg("H"), py::arg("W"));
+  m.def("lap_merge", &lap_merge, "Laplacian pyramid merge with explicit or partial-derived per-image scales",
+        py::arg("lo_n"), py::arg("hi"), py::arg("merged"), py::arg("out"), py::arg("scales") = py::none(),
+        py::arg("hpart") = std::vector<Tensor>(), py::arg("lpart") = py::none(), py::arg("eps") = 1e-10);
+  m.def("lap_normalize", &lap_normalize, "Laplacian-pyramid normalisation of a gradient: split + merge (2n launches)",
+        py::arg("g"), py::arg("lo"), py::arg("hi"), py::arg("hpart"), py::arg("lpart"), py::arg("merged"),
+        py::arg("out"), py::arg("eps") = 1e-10);
   m.def("dream_update", &dream_update, "fused DeepDream normalize + update + next network input");
   m.def("octave_resize", &octave_resize, "DeepDream octave transition: corner-aligned bilinear resize of (a + b - c)",
         py::arg("a"), py::arg("b"), py::arg("c"), py::arg("y"), py::arg("yin") = py::none());

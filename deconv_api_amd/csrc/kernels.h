@@ -278,6 +278,23 @@ int dream_update_launch(const uint16_t* g, float* x, uint16_t* xin, float* gpart
 // be null), optionally also written as the 16-bit 8-channel network input yin
 int octave_resize_launch(const float* a, const float* b, const float* c, float* y, uint16_t* yin, int N, int Hs, int Ws, int Hd, int Wd,
                          int dtype, hipStream_t s);
+// Laplacian-pyramid gradient normalisation (dream_lap.hip), one level per launch. A level's maps are cut into
+// LAP_TILE_H x LAP_TILE_W tiles, one block and one partial each: parts = lap_tiles(H) * lap_tiles_w(W).
+// src / dst: DT_BF16 / DT_F16 = the 16-bit 8-channel layout [N,H,W,8] (channels 0..2 used, 3..7 written as
+// zero), LAP_F32 = fp32 [N,H,W,3].
+constexpr int LAP_TILE_H = 16, LAP_TILE_W = 32, LAP_F32 = 2, LAP_MAX_LEVELS = 5;
+inline int lap_tiles(int H) { return (H + LAP_TILE_H - 1) / LAP_TILE_H; }
+inline int lap_tiles_w(int W) { return (W + LAP_TILE_W - 1) / LAP_TILE_W; }
+// split: lo [N,ceil(H/2),ceil(W/2),3] = down(x), hi [N,H,W,3] = x - up(lo), hpart [N][parts] = block partials of
+// sum hi^2; lpart (null unless this is the last level) [N][parts] = partials of sum lo^2
+int lap_split_launch(const void* x, int src, float* lo, float* hi, float* hpart, float* lpart, int N, int H, int W,
+                     hipStream_t s);
+// merge: out [N,H,W,*] = up(sp * prev) + sh * hi. scales ([N][S], explicit): sh = scales[n][si], sp = scales[n][0]
+// if first else 1; scales null: sh = 1 / max(sqrt(sum hpart[n][:hparts] / (3 H W)), eps), sp the same from ppart
+// over prev's elements if first (prev is the coarsest lo) else 1
+int lap_merge_launch(const float* prev, const float* hi, void* out, int dst, const float* scales, int S, int si,
+                     const float* hpart, int hparts, const float* ppart, int pparts, float eps, int first, int N, int H,
+                     int W, hipStream_t s);
 // tiled DeepDream step: rolled tile gather -> owned-pixel pack (+ unit loss / sum|g| tail) ->
 // [all-gather of packs over ranks] -> update of the fp32 image straight from the packs
 int tile_gather_launch(const float* x, uint16_t* xin, const int* plan, const int* shift, int units, int rank, int world,

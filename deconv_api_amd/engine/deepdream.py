@@ -29,7 +29,7 @@ import torch
 import torch.nn.functional as F
 
 from .. import knobs
-from ..ops import native
+from ..ops import lapnorm, native
 from ..runtime.capture import capture
 from ..utils.logging import get_logger
 from ..ops.autograd import _is_relu_out, guide_core, guide_index, guide_tap, loss_tap, premasked_grads, sumsq_core
@@ -91,6 +91,9 @@ class DreamSettings:
     max_loss: Optional[float] = 10.0
     border: int = 2  # act[:, 2:-2, 2:-2, :]
     guide_size: int = 224  # a guide image is resized to this side before its features are taken
+    # > 0: every step's gradient is Laplacian-pyramid normalised over this many levels before the mean-|g|
+    # division (ops/lapnorm.py; 1..5). 0: the plain step, launch for launch
+    lap_levels: int = 0
 
 
 def resize(x: torch.Tensor, hw: Tuple[int, int]) -> torch.Tensor:
@@ -171,8 +174,16 @@ class DeepDream:
             feats = {n: acts[n].detach().reshape(G, -1, acts[n].shape[3]).contiguous() for n in self.s.layers}
         return GuideFeatures(feats, guide_index([0] * B if G == 1 else range(B), G, self.device))
 
+    def _lap(self) -> int:
+        """The validated ``lap_levels`` setting (it may be set per batch by the service)."""
+        n = self.s.lap_levels
+        if isinstance(n, bool) or not isinstance(n, int) or not 0 <= n <= lapnorm.MAX_LEVELS:
+            raise ValueError(f"lap_levels must be an integer in 0..{lapnorm.MAX_LEVELS}, got {n!r}")
+        return n
+
     def loss_and_grad(self, x: torch.Tensor, guide_feats: Optional[GuideFeatures] = None):
-        """x: fp32 [B, H, W, 3] (preprocessed). Returns (loss [B], normalized grad [B, H, W, 3])."""
+        """x: fp32 [B, H, W, 3] (preprocessed). Returns (loss [B], normalized grad [B, H, W, 3]); with
+        ``lap_levels`` the gradient is Laplacian-pyramid normalised (torch reference) before the mean-|g| division."""
         xin = self._net_input(x).requires_grad_(True)
         # the loss gradient (2*act/numel, or the guide row masked by act > 0) vanishes where act does
         with premasked_grads():
@@ -180,6 +191,9 @@ class DeepDream:
         loss = self.loss(acts, guide_feats)
         (g,) = torch.autograd.grad(loss.sum(), xin)
         g = g[..., :3].float()
+        if self._lap():
+            # (rounded to the engine's dtype as the fused step's 16-bit gradient layout is; fp32 on the CPU: exact)
+            g = lapnorm.normalize_ref(g, self._lap()).to(xin.dtype).float()
         g = g / g.abs().mean(dim=(1, 2, 3), keepdim=True).clamp_min(1e-7)
         return loss.detach(), g
 
@@ -191,11 +205,12 @@ class DeepDream:
         return loss
 
     # ------------------------------------------------------------------ fused GPU step
-    def _state(self, B: int, hw: Tuple[int, int], gkey: Optional[tuple] = None):
+    def _state(self, B: int, hw: Tuple[int, int], gkey: Optional[tuple] = None, lap: int = 0):
         """Static buffers of one octave shape: fp32 master image x, the 16-bit network input xin
         (an autograd leaf), loss/|g| partials, per-layer loss scales, done/loss flags; for a guided
         dream (``gkey``: the layers' [G, Q, C]) also the guide features and the guide-of-row table,
-        which a captured graph reads: they are copied into before every replay."""
+        which a captured graph reads: they are copied into before every replay; with ``lap`` levels the
+        pyramid's level buffers, partials and the normalised 16-bit gradient."""
         dev = self.device
         names = list(self.s.layers.keys())
         st = type("DreamState", (), {})()
@@ -209,6 +224,10 @@ class DeepDream:
         st.scales = None
         st.graph = None
         st.guide = None
+        st.lap, st.lap_out = None, None
+        if lap:
+            st.lap = lapnorm.LapBuffers(B, hw[0], hw[1], lap, dev)
+            st.lap_out = torch.empty(B, *hw, 8, device=dev, dtype=self.dtype)
         if gkey is not None:
             st.guide = GuideFeatures({n: torch.zeros(*shp, device=dev, dtype=self.dtype) for n, shp in zip(names, gkey)},
                                      torch.zeros(B, dtype=torch.int32, device=dev))
@@ -277,9 +296,12 @@ class DeepDream:
 
     def _fused_step(self, st) -> None:
         """forward -> per-layer sumsq partials + loss gradients (HIP) -> autograd backward of the
-        network only -> one fused normalize/update kernel that also writes the next xin."""
+        network only -> [lap_levels: Laplacian-pyramid normalisation of the gradient, one split and one merge
+        launch per level, csrc/dream_lap.hip] -> one fused normalize/update kernel that also writes the next xin."""
         lib = native.lib()
         g = self._loss_grad(st, st.xin)
+        if st.lap is not None:
+            g = lapnorm.lap_normalize(g.contiguous(), st.lap.n, buffers=st.lap, out=st.lap_out)
         ml = -1.0 if self.s.max_loss is None else float(self.s.max_loss)
         lib.dream_update(g.contiguous(), st.x, st.xin, st.gpart, st.lpart, st.lcoef, st.done, st.loss,
                          float(self.s.step), ml)
@@ -296,12 +318,15 @@ class DeepDream:
     def _fused_state(self, B: int, hw: Tuple[int, int], guide_feats: Optional[GuideFeatures] = None):
         steps = self.s.iterations if OCTAVE_GRAPH else 1
         key = (B, tuple(hw), steps, self._slot)
+        lap = self._lap()
+        if lap:  # other launches and its own level buffers (0: the key, state and graph of the plain step)
+            key += ("lap", lap)
         if guide_feats is not None:  # a guided graph has other launches and reads the guide buffers
             key += ("guided", guide_feats.key())
         if key in self._graphs:
             self._graphs.move_to_end(key)
             return self._load_guide(self._graphs[key], guide_feats)
-        st = self._load_guide(self._state(B, hw, None if guide_feats is None else guide_feats.key()), guide_feats)
+        st = self._load_guide(self._state(B, hw, None if guide_feats is None else guide_feats.key(), lap), guide_feats)
         if self.use_graphs:
             s = torch.cuda.Stream(self.device)
             s.wait_stream(torch.cuda.current_stream(self.device))
@@ -323,7 +348,7 @@ class DeepDream:
 
     # ------------------------------------------------------------------ hipGraph per shape
     def _graph(self, B: int, hw: Tuple[int, int]):
-        key = (B, tuple(hw))
+        key = (B, tuple(hw)) + (("lap", self._lap()) if self._lap() else ())
         if key in self._graphs:
             self._graphs.move_to_end(key)
             return self._graphs[key]
@@ -531,7 +556,13 @@ class TiledDeepDream(DeepDream):
     def run(self, x: torch.Tensor, guide: Optional[torch.Tensor] = None) -> torch.Tensor:
         if guide is not None:
             raise ValueError("guide is not supported by the tiled engine")
+        self._refuse_lap()
         return super().run(x)
+
+    def _refuse_lap(self) -> None:
+        """Laplacian-pyramid normalisation works on a whole image's gradient; the tiled step never holds one."""
+        if self.s.lap_levels:
+            raise ValueError("lap_levels is not supported by the tiled engine")
 
     @staticmethod
     def _axis_tiles(L: int, tile: int):
@@ -830,6 +861,7 @@ class TiledDeepDream(DeepDream):
         transition is ONE octave_resize launch straight into the next octave's static fp32 image (the
         tiles gather their 16-bit inputs from it), as the untiled fused path does; the generic path
         (F.interpolate x4 + two adds per transition) is the CPU / DV_DREAM_OCTAVE_RESIZE=0 oracle."""
+        self._refuse_lap()
         if self.tile_fused and x.is_cuda and OCTAVE_RESIZE:
             yield from self._tiled_octave_steps_fused(x)
             return

@@ -15,7 +15,9 @@ H, W) key (waiting up to ``dream_window_ms`` for more, at most ``dream_max_batch
 as ONE DeepDream batch. A request may carry a GUIDE image (guided DeepDream: the image dreams towards
 the guide's features, engine/deepdream.py): it is decoded and resized to the engine's ``guide_size`` on
 the codec threads, guided and unguided requests batch apart (``guided`` is part of the key), and the
-guides are stacked like the images. Guided dreams run on the untiled one-GPU engine only. Every image's loss, gradient normalisation and max-loss flag are per
+guides are stacked like the images. Guided dreams run on the untiled one-GPU engine only. So do requests
+with ``lap_levels`` > 0 (Laplacian-pyramid gradient normalisation, ops/lapnorm.py): the level count is part of
+the key too, and the engine's setting is set per batch. Every image's loss, gradient normalisation and max-loss flag are per
 image (engine/deepdream.py), so batching is exact; the batch is padded to a power of two by
 repeating the last image so the per-(B, H, W) hipGraph cache sees few distinct batch sizes."""
 from __future__ import annotations
@@ -42,7 +44,7 @@ MODELS = ("inception_v3", "resnet50")
 @dataclass
 class _Req:
     img: torch.Tensor  # u8 [H, W, 3], already resized to <= MAX_SIDE
-    key: Tuple[Any, ...]  # (model, octaves, steps, H, W, guided)
+    key: Tuple[Any, ...]  # (model, octaves, steps, H, W, guided, lap_levels)
     fut: asyncio.Future
     loop: asyncio.AbstractEventLoop
     t0: float = field(default_factory=time.perf_counter)
@@ -121,17 +123,19 @@ class DreamService:
 
     # ------------------------------------------------------------------ engines
     @staticmethod
-    def validate(model: str, octaves: int, steps: int) -> None:
+    def validate(model: str, octaves: int, steps: int, lap_levels: int = 0) -> None:
         if model not in MODELS:
             raise ValueError("model must be inception_v3 or resnet50")
         if not (1 <= octaves <= 6 and 1 <= steps <= 100):
             raise ValueError("octaves must be 1..6 and steps 1..100")
+        if isinstance(lap_levels, bool) or not isinstance(lap_levels, int) or not 0 <= lap_levels <= 5:
+            raise ValueError("lap_levels must be 0..5")
 
-    def engine(self, model: str, octaves: int, steps: int) -> DeepDream:
+    def engine(self, model: str, octaves: int, steps: int, lap_levels: int = 0) -> DeepDream:
         """The untiled engine of ``model``. Its settings are set per batch, so it is only handed out
         under ``_run_lock``, which ``run_batch`` holds for the whole batch (a second thread's batch
         waits instead of changing octaves / steps under a running one)."""
-        self.validate(model, octaves, steps)
+        self.validate(model, octaves, steps, lap_levels)
         assert self._run_lock._is_owned(), "DreamService.engine: hold _run_lock (run_batch does)"
         with self._lock:
             if model not in self._engines:
@@ -140,7 +144,7 @@ class DreamService:
                 s = dream_settings(model, octaves, steps)
                 self._engines[model] = DeepDream(self._nets[model], s, use_graphs=self.cfg.hip_graphs)
             e = self._engines[model]
-        e.s.octaves, e.s.iterations = octaves, steps
+        e.s.octaves, e.s.iterations, e.s.lap_levels = octaves, steps, lap_levels
         return e
 
     def tiled(self, model: str, octaves: int, steps: int) -> TiledDeepDream:
@@ -191,6 +195,13 @@ class DreamService:
         if max(H, W) > self.cfg.dream_tile:
             raise ValueError(f"guide is not supported by the tiled engine (image side > {self.cfg.dream_tile})")
 
+    def check_lap(self, H: int, W: int) -> None:
+        """``lap_levels`` > 0 runs on the untiled one-GPU engine only (ValueError: the route's 400)."""
+        if self.world > 1:
+            raise ValueError("lap_levels is not supported by a multi-rank service")
+        if max(H, W) > self.cfg.dream_tile:
+            raise ValueError(f"lap_levels is not supported by the tiled engine (image side > {self.cfg.dream_tile})")
+
     # ------------------------------------------------------------------ batching worker
     def _ensure_worker(self) -> None:
         with self._cv:
@@ -221,23 +232,27 @@ class DreamService:
             return batch
 
     def run_batch(self, imgs: List[torch.Tensor], model: str, octaves: int, steps: int,
-                  guides: Optional[List[torch.Tensor]] = None) -> np.ndarray:
+                  guides: Optional[List[torch.Tensor]] = None, lap_levels: int = 0) -> np.ndarray:
         """u8 [H, W, 3] images of one shape -> dreamed u8 [n, H, W, 3] (one engine batch): across
         every rank when the service has several, tiled on this GPU for sides > dream_tile, else the
-        untiled engine. ``guides``: one prepared guide (``prepare_guide``) per image."""
+        untiled engine. ``guides``: one prepared guide (``prepare_guide``) per image. ``lap_levels`` > 0:
+        Laplacian-pyramid gradient normalisation over that many levels (untiled one-GPU engine only)."""
         with self._run_lock:
-            return self._run_batch(imgs, model, octaves, steps, guides)
+            return self._run_batch(imgs, model, octaves, steps, guides, lap_levels)
 
     def _run_batch(self, imgs: List[torch.Tensor], model: str, octaves: int, steps: int,
-                   guides: Optional[List[torch.Tensor]] = None) -> np.ndarray:
+                   guides: Optional[List[torch.Tensor]] = None, lap_levels: int = 0) -> np.ndarray:
         n = len(imgs)
         t0 = time.perf_counter()
         H, W = imgs[0].shape[:2]
+        self.validate(model, octaves, steps, lap_levels)
+        if lap_levels:
+            self.check_lap(H, W)
         if guides is not None:
             if len(guides) != n:
                 raise ValueError("one guide per image")
             self.check_guided(H, W)
-            e = self.engine(model, octaves, steps)
+            e = self.engine(model, octaves, steps, lap_levels)
             pad = _bucket(n, self.max_batch) - n
             x = torch.stack(imgs + [imgs[-1]] * pad)
             g = torch.stack(list(guides) + [guides[-1]] * pad)  # padding repeats the last guide
@@ -249,7 +264,7 @@ class DreamService:
             e.gen.manual_seed(self.cfg.seed)  # same rolls as the multi-rank path for the same input
             out = e.dream_u8(torch.stack(imgs)).cpu().numpy()
         else:
-            e = self.engine(model, octaves, steps)
+            e = self.engine(model, octaves, steps, lap_levels)
             pad = _bucket(n, self.max_batch) - n
             x = torch.stack(imgs + [imgs[-1]] * pad)
             out = e.dream_u8(x)[:n].cpu().numpy()
@@ -266,8 +281,9 @@ class DreamService:
             model, octaves, steps = batch[0].key[:3]
             self.batches.append(len(batch))
             guides = [r.guide for r in batch] if batch[0].guide is not None else None
+            kw = {"lap_levels": batch[0].key[6]} if batch[0].key[6] else {}
             try:
-                out = self.run_batch([r.img for r in batch], model, octaves, steps, guides)
+                out = self.run_batch([r.img for r in batch], model, octaves, steps, guides, **kw)
             except Exception as exc:  # noqa: BLE001 - delivered to every request of the batch
                 for r in batch:
                     r.loop.call_soon_threadsafe(_resolve, r.fut, None, exc)
@@ -284,20 +300,23 @@ class DreamService:
 
     # ------------------------------------------------------------------ request entry
     async def dream(self, uri: str, model: str = "inception_v3", octaves: int = 4, steps: int = 20,
-                    guide: Optional[str] = None) -> str:
-        """``guide`` (optional): data URL of the image to dream towards."""
-        self.validate(model, octaves, steps)
+                    guide: Optional[str] = None, lap_levels: int = 0) -> str:
+        """``guide`` (optional): data URL of the image to dream towards. ``lap_levels`` (0..5): levels of the
+        Laplacian-pyramid gradient normalisation, 0 = off."""
+        self.validate(model, octaves, steps, lap_levels)
         loop = asyncio.get_running_loop()
         img = await loop.run_in_executor(None, read_data_url, uri)
         t = await loop.run_in_executor(None, self.prepare, img, octaves)
         g = None
+        if lap_levels:
+            self.check_lap(t.shape[0], t.shape[1])
         if guide is not None:
             self.check_guided(t.shape[0], t.shape[1])
             g = await loop.run_in_executor(None, lambda: self.prepare_guide(read_data_url(guide)))
         fut = loop.create_future()
         self._ensure_worker()
         with self._cv:
-            key = (model, octaves, steps, t.shape[0], t.shape[1], g is not None)
+            key = (model, octaves, steps, t.shape[0], t.shape[1], g is not None, lap_levels)
             self._pending.append(_Req(t, key, fut, loop, guide=g))
             M.QUEUE_DEPTH.set(len(self._pending), route="/deepdream")
             self._cv.notify_all()

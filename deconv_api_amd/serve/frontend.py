@@ -133,10 +133,13 @@ class RemoteDream(_Remote):
     """``DreamService.dream`` forwarded to the GPU owner (which validates and decodes)."""
 
     async def dream(self, uri: str, model: str = "inception_v3", octaves: int = 4, steps: int = 20,
-                    guide: str = None) -> str:
+                    guide: str = None, lap_levels: int = 0) -> str:
         """Body: JSON header, newline, the image's data URL and - for a guided dream - the guide's data URL
-        right behind it, its length in the header's ``guide_len`` (absent for an unguided request)."""
+        right behind it, its length in the header's ``guide_len`` (absent for an unguided request);
+        ``lap_levels`` is in the header only when it is not 0."""
         head = {"model": model, "octaves": octaves, "steps": steps}
+        if lap_levels:
+            head["lap_levels"] = lap_levels
         tail = b""
         if guide is not None:
             tail = guide.encode()

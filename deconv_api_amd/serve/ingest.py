@@ -239,6 +239,12 @@ class IngestServer:
         if glen:
             uri, guide = uri[:-glen], uri[-glen:]
             kw["guide"] = guide.decode("ascii", errors="replace")
+        lap = p.get("lap_levels", 0)  # Laplacian-pyramid levels; absent = 0 = the plain step
+        if isinstance(lap, bool) or not isinstance(lap, int) or not 0 <= lap <= 5:
+            reply(rid, 400, b"bad dream header")
+            return
+        if lap:
+            kw["lap_levels"] = lap
         loop = self._dream_loop()
         fut = asyncio.run_coroutine_threadsafe(
             self.dream.dream(uri.decode("ascii", errors="replace"), p["model"], int(p["octaves"]), int(p["steps"]),
