@@ -103,3 +103,30 @@ def _pool_case(g, N, H, W, C, OC, taps=96):
     _check_exact(full, BF, x, cw, 4.0)
     _check_ties(full)
     return x, cw, rp, rc
+
+
+def _representable(ref, what="reference"):
+    """``ref`` (fp32 / fp64) is exactly representable in both 16-bit storage types."""
+    for dt in (BF, HF):
+        assert torch.equal(ref.detach().to(dt).double(), ref.detach().double()), f"{what} not representable in {dt}"
+
+
+def _tap_weights(g, oc, c, kh=1, kw=1, taps=6, lim=1, live=None):
+    """OIHW integer weights, non-zero values in [-lim, lim], thinned like ``_weights`` to about ``taps``
+    non-zero taps per output, all of them on the first ``live`` input channels (default: every channel)."""
+    live = c if live is None else live
+    shape = (oc, c, kh, kw)
+    w = _ints(g, shape, 1, lim) * (2 * torch.randint(0, 2, shape, generator=g) - 1)
+    w = w * (torch.rand(shape, generator=g) < taps / (live * kh * kw))
+    w[:, live:] = 0
+    return w
+
+
+def _recip_exact(m, cnt):
+    """The pool kernels' fp32 formula m * (1.f / count) equals the exact integer quotient m / count (m fp32
+    integers, cnt the window counts, broadcastable); returns the fp32 result."""
+    inv = torch.ones((), dtype=torch.float32) / cnt.float()
+    q = m.float() * inv
+    assert torch.equal(q.double(), m.double() / cnt.double()), "sum * (1.f / count) is not the exact average"
+    assert torch.equal(q, q.round()), "average is not an integer"
+    return q
