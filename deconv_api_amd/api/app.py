@@ -9,11 +9,13 @@
   ``Form(...)`` needs python-multipart, which is not installed)
 
 Extensions: GET /ready (per-device status), GET /metrics (Prometheus text), GET /layers,
-POST /deepdream (when the DeepDream engine is available).
+POST /deepdream (when the DeepDream engine is available), POST /occlusion (occlusion sensitivity maps of the
+filters POST / reconstructs; engine/occlusion.py).
 
 Error handling differs deliberately from the reference (which 500s on all of these):
 missing fields -> 422 (FastAPI's own validation shape), undecodable image / malformed data URL /
-unknown layer -> 400, queue full -> 503; fewer than 4 positive filters -> black tiles.
+unknown layer (and, on /occlusion, a bad patch / stride) -> 400, queue full -> 503; fewer than 4
+positive filters -> black tiles.
 """
 from __future__ import annotations
 
@@ -44,6 +46,32 @@ _FORM_SCHEMA = {
         },
     }
 }
+
+
+_OCC_SCHEMA = {
+    "requestBody": {
+        "required": True,
+        "content": {
+            ct: {"schema": {"title": "Body_occlusion_occlusion_post", "type": "object", "required": ["file", "layer"],
+                            "properties": {"file": {"title": "File", "type": "string"},
+                                           "layer": {"title": "Layer", "type": "string"},
+                                           "patch": {"title": "Patch", "type": "integer", "default": 32},
+                                           "stride": {"title": "Stride", "type": "integer", "default": 16}}}}
+            for ct in ("application/x-www-form-urlencoded", "multipart/form-data")
+        },
+    }
+}
+
+
+def _form_int(form, name: str, default: int) -> int:
+    """An optional decimal integer field; ValueError (-> 400) for anything else."""
+    v = form.get(name)
+    if v is None or v == "":
+        return default
+    v = v.strip()
+    if not (v.isascii() and v.lstrip("+-").isdigit() and len(v) <= 9):
+        raise ValueError(f"{name} must be an integer, got {v!r}")
+    return int(v)
 
 
 def _missing(fields):
@@ -141,6 +169,53 @@ def create_app(service=None, cfg: Optional[Config] = None, dream_service=None) -
         finally:
             M.REQUESTS.inc(route="/", status=status)
             M.LATENCY.observe(time.perf_counter() - t0, route="/", layer=layer)
+
+    @app.post("/occlusion", openapi_extra=_OCC_SCHEMA)
+    async def occlusion(request: Request):
+        """Extension (not in the reference): occlusion sensitivity maps (Zeiler & Fergus section 4.2) of the four
+        filters ``POST /`` would reconstruct. Form fields: file, layer, optional patch (default 32) and stride
+        (default 16): 8 <= patch <= image side / 2, 4 <= stride <= patch, at most 255 patch positions. The
+        response has the shape of ``POST /``: the 2x2 mosaic (true RGB) as a JPEG data URL."""
+        t0 = time.perf_counter()
+        status, layer = "200", "-"
+        try:
+            try:
+                form = parse_form(await request.body(), request.headers.get("content-type"))
+            except FormError as e:
+                status = "400"
+                return JSONResponse(status_code=400, content={"detail": str(e)})
+            missing = [f for f in ("file", "layer") if f not in form]
+            if missing:
+                status = "422"
+                return _missing(missing)
+            layer = form["layer"]
+            svc = get_service()
+            try:
+                patch, stride = (_form_int(form, f, d) for f, d in (("patch", 32), ("stride", 16)))
+                url = await svc.occlusion(form["file"], layer, patch, stride)
+            except UnknownLayerError as e:
+                status = "400"
+                return JSONResponse(status_code=400, content={"detail": str(e).strip('"')})
+            except (ImageDecodeError, ValueError) as e:
+                status = "400"
+                return JSONResponse(status_code=400, content={"detail": str(e)})
+            except Exception as e:  # noqa: BLE001
+                from ..serve.service import ServiceOverloaded
+
+                code = getattr(e, "status", None)  # serve/frontend.py RemoteError: the GPU owner's answer
+                if isinstance(code, int) and code != 500:
+                    status = str(code)
+                    return JSONResponse(status_code=code, content={"detail": str(e)})
+                if isinstance(e, ServiceOverloaded):
+                    status = "503"
+                    return JSONResponse(status_code=503, content={"detail": str(e)})
+                status = "500"
+                log.exception("occlusion request failed")
+                return JSONResponse(status_code=500, content={"detail": "internal error"})
+            return _json_string_response(url)
+        finally:
+            M.REQUESTS.inc(route="/occlusion", status=status)
+            M.LATENCY.observe(time.perf_counter() - t0, route="/occlusion", layer=layer)
 
     @app.get("/ready")
     def ready():

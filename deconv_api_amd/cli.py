@@ -3,13 +3,16 @@
     python -m deconv_api_amd.cli deconv photo.jpg [more.png ...] --layer block5_conv3 [--out-dir out/]
     python -m deconv_api_amd.cli dream photo.jpg --model inception_v3 --octaves 4 --steps 20 [--out-dir out/]
                                        [--guide other.jpg] [--lap-levels 4]
+    python -m deconv_api_amd.cli occlusion photo.jpg --layer block5_conv3 [--patch 32 --stride 16] [--out-dir out/]
     python -m deconv_api_amd.cli layers
 
 ``deconv`` writes ``<stem>_<layer>.jpg``: the 2x2 mosaic of the top-4 deconvnet reconstructions, the same
 image ``POST /`` returns as a data URL (reference: app/main.py:45-78), all files as one batch on the device.
 ``dream`` writes ``<stem>_dream_<model>.jpg`` (``POST /deepdream``); with ``--guide`` every image dreams towards
 that image's features (the route's ``guide`` field), with ``--lap-levels N`` the gradient of every step is
-Laplacian-pyramid normalised over N levels (the route's ``lap_levels`` field). Configuration as the server's
+Laplacian-pyramid normalised over N levels (the route's ``lap_levels`` field). ``occlusion`` writes
+``<stem>_occlusion_<layer>.jpg``: the JPEG ``POST /occlusion`` returns (occlusion sensitivity maps of the same four
+filters, one image after another). Configuration as the server's
 (``DV_*`` variables, config.py) with ``--device`` / ``--dtype`` / ``--weights`` overrides.
 """
 from __future__ import annotations
@@ -66,6 +69,47 @@ def cmd_deconv(a, cfg) -> int:
     return 0
 
 
+def _route_jpeg(svc, mos) -> bytes:
+    """The JPEG inside the data URL the service's routes answer with for the one-image result ``mos``: encoded the
+    way serve/service.py's ``_encode_deliver`` does (GPU scans, the native encoder's restart segments, or PIL)."""
+    import base64
+    from urllib.parse import unquote
+
+    from .codec import encode_data_url, encode_data_urls
+    from .codec.image import gpu_data_urls
+    from .runtime.staging import GpuScans
+
+    q, th = svc.cfg.jpeg_quality, svc.cfg.encode_threads
+    if isinstance(mos, GpuScans):
+        url = gpu_data_urls(mos.packed, mos.off, mos.H, mos.W, q, th)[0]
+    elif svc.native_codec:
+        url = encode_data_urls(mos[:1], q, th)[0]
+    else:
+        url = encode_data_url(mos[0], q)
+    if not isinstance(url, str):
+        url = bytes(url).decode("ascii")
+    return base64.b64decode(unquote(url.split(",", 1)[1]))
+
+
+def cmd_occlusion(a, cfg) -> int:
+    from .serve.service import DeconvService
+
+    svc = DeconvService(cfg)
+    try:
+        svc.validate_occlusion(a.layer, a.patch, a.stride)  # fails before any decode or compute
+        outs = [svc.run_occlusion(a.layer, img, a.patch, a.stride) for img in _read(a.images)]
+    finally:
+        svc.close()
+    os.makedirs(a.out_dir, exist_ok=True)
+    for p, mos in zip(a.images, outs):
+        jpeg = _route_jpeg(svc, mos)
+        dst = os.path.join(a.out_dir, f"{_stem(p)}_occlusion_{a.layer}.jpg")
+        with open(dst, "wb") as f:
+            f.write(jpeg)
+        print(dst)
+    return 0
+
+
 def cmd_dream(a, cfg) -> int:
     from .codec import encode_jpeg
     from .serve.dream_service import DreamService
@@ -116,6 +160,12 @@ def main(argv=None) -> int:
     r.add_argument("--lap-levels", type=int, default=0, choices=range(6), metavar="N",
                    help="Laplacian-pyramid gradient normalisation over N levels (0..5, 0 = off)")
     r.add_argument("--out-dir", default=".")
+    o = sub.add_parser("occlusion", help="occlusion sensitivity mosaic of each image")
+    o.add_argument("images", nargs="+")
+    o.add_argument("--layer", default="block5_conv3")
+    o.add_argument("--patch", type=int, default=32, help="side of the grey square (8 .. half the image side)")
+    o.add_argument("--stride", type=int, default=16, help="step of the square (4 .. patch)")
+    o.add_argument("--out-dir", default=".")
     sub.add_parser("layers", help="the VGG16 layer names POST / accepts")
     a = ap.parse_args(argv)
 
@@ -129,7 +179,7 @@ def main(argv=None) -> int:
     from .engine.deconvnet import UnknownLayerError
 
     try:
-        return {"deconv": cmd_deconv, "dream": cmd_dream, "layers": cmd_layers}[a.cmd](a, cfg)
+        return {"deconv": cmd_deconv, "dream": cmd_dream, "occlusion": cmd_occlusion, "layers": cmd_layers}[a.cmd](a, cfg)
     except (UnknownLayerError, ImageDecodeError, ValueError, OSError) as e:  # the HTTP routes' 400s
         print(f"error: {str(e).strip(chr(34))}", file=sys.stderr)
         return 2

@@ -939,6 +939,85 @@ void lap_normalize(Tensor g, std::vector<Tensor> lo, std::vector<Tensor> hi, std
   lap_merge(lo.back(), hi, merged, out, c10::nullopt, hpart, lpart, eps);
 }
 
+// Occlusion sensitivity (occlusion.hip; geometry in kernels.h). x0: the 16-bit network input [B,S,S,8].
+static int64_t occ_g(int64_t S, int64_t patch, int64_t stride, const char* what) {
+  TORCH_CHECK(S >= 1 && S <= 4096 && patch >= 0 && patch <= 4096 && stride >= 0 && stride <= 4096, what,
+              ": S, patch, stride out of range");
+  const int g = dv::occ_grid((int)S, (int)patch, (int)stride);
+  TORCH_CHECK(g > 0, what, ": needs 16 <= S <= 4096, 8 <= patch <= S / 2, 4 <= stride <= patch and at most ",
+              dv::OCC_MAX_P, " patches; got S ", S, ", patch ", patch, ", stride ", stride);
+  return g;
+}
+
+static void occ_x0(const Tensor& x0, const char* what) {
+  check_cuda(x0, what);
+  TORCH_CHECK(is16(x0) && x0.dim() == 4 && x0.is_contiguous() && x0.size(0) >= 1 && x0.size(0) <= 65535 &&
+                  x0.size(1) == x0.size(2) && x0.size(3) == 8 && reinterpret_cast<uintptr_t>(x0.data_ptr()) % 16 == 0,
+              what, ": contiguous, 16-B aligned bf16 / fp16 [B, S, S, 8]");
+}
+
+static void occ_like(const Tensor& t, const Tensor& like, at::ScalarType dt, std::vector<int64_t> shape, const char* what) {
+  check_cuda(t, what);
+  TORCH_CHECK(t.scalar_type() == dt && t.is_contiguous() && t.sizes() == at::IntArrayRef(shape) &&
+                  t.device() == like.device(),
+              what, ": contiguous ", dt, " ", at::IntArrayRef(shape), " on ", like.device(), " expected, got ",
+              t.scalar_type(), " ", t.sizes());
+  need(t, t.numel() * (int64_t)t.element_size(), what);
+}
+
+int64_t occlusion_parts(int64_t S) {
+  TORCH_CHECK(S >= 1 && S <= 4096, "occlusion_parts: 1 <= S <= 4096");
+  return dv::occ_parts((int)S);
+}
+
+void occlude_variants(Tensor x0, Tensor xv, int64_t patch, int64_t stride) {
+  occ_x0(x0, "occlude_variants: x0");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x0.device());
+  const int64_t B = x0.size(0), S = x0.size(1), g = occ_g(S, patch, stride, "occlude_variants");
+  occ_like(xv, x0, x0.scalar_type(), {B * (g * g + 1), S, S, 8}, "occlude_variants: xv");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(xv.data_ptr()) % 16 == 0, "occlude_variants: xv must be 16-byte aligned");
+  need(x0, x0.numel() * 2, "occlude_variants: x0");
+  check_rc(dv::occlude_variants_launch(reinterpret_cast<const uint16_t*>(x0.data_ptr()),
+                                       reinterpret_cast<uint16_t*>(xv.data_ptr()), (int)B, (int)S, (int)patch,
+                                       (int)stride, cur_stream()),
+           "occlude_variants");
+}
+
+void occlusion_heat(Tensor scores, Tensor idx, Tensor heat, Tensor part, int64_t patch, int64_t stride) {
+  check_cuda(heat, "occlusion_heat: heat");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(heat.device());
+  TORCH_CHECK(heat.dim() == 4 && heat.size(0) >= 1 && heat.size(0) <= 65535 && heat.size(1) == 4 &&
+                  heat.size(2) == heat.size(3),
+              "occlusion_heat: heat [B, 4, S, S]");
+  const int64_t B = heat.size(0), S = heat.size(2), g = occ_g(S, patch, stride, "occlusion_heat");
+  TORCH_CHECK(scores.dim() == 3 && scores.size(2) >= 1 && (g * g + 1) * scores.size(2) <= 0x7FFFFFFFLL,
+              "occlusion_heat: scores [B, P + 1, C]");
+  occ_like(heat, heat, at::kFloat, {B, 4, S, S}, "occlusion_heat: heat");
+  occ_like(scores, heat, at::kFloat, {B, g * g + 1, scores.size(2)}, "occlusion_heat: scores");
+  occ_like(idx, heat, at::kInt, {B, 4}, "occlusion_heat: idx");
+  occ_like(part, heat, at::kFloat, {B, 4, dv::occ_parts((int)S)}, "occlusion_heat: part");
+  check_rc(dv::occlusion_heat_launch(scores.data_ptr<float>(), idx.data_ptr<int>(), heat.data_ptr<float>(),
+                                     part.data_ptr<float>(), (int)B, (int)scores.size(2), (int)S, (int)patch,
+                                     (int)stride, cur_stream()),
+           "occlusion_heat");
+}
+
+void occlusion_overlay(Tensor heat, Tensor part, Tensor idx, Tensor x0, Tensor out) {
+  occ_x0(x0, "occlusion_overlay: x0");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(x0.device());
+  const int64_t B = x0.size(0), S = x0.size(1);
+  TORCH_CHECK(S >= 16 && S <= 4096, "occlusion_overlay: 16 <= S <= 4096");
+  need(x0, x0.numel() * 2, "occlusion_overlay: x0");
+  occ_like(heat, x0, at::kFloat, {B, 4, S, S}, "occlusion_overlay: heat");
+  occ_like(part, x0, at::kFloat, {B, 4, dv::occ_parts((int)S)}, "occlusion_overlay: part");
+  occ_like(idx, x0, at::kInt, {B, 4}, "occlusion_overlay: idx");
+  occ_like(out, x0, at::kByte, {B, 2 * S, 2 * S, 3}, "occlusion_overlay: out");
+  check_rc(dv::occlusion_overlay_launch(heat.data_ptr<float>(), part.data_ptr<float>(), idx.data_ptr<int>(),
+                                        reinterpret_cast<const uint16_t*>(x0.data_ptr()), out.data_ptr<uint8_t>(),
+                                        (int)B, (int)S, dt_of(x0), cur_stream()),
+           "occlusion_overlay");
+}
+
 // Fused DeepDream update (engine/deepdream.py): g [N,H,W,8] 16-bit input gradient, x [N,H,W,3] fp32
 // master image (updated in place), xin [N,H,W,8] next network input, gpart [N, P] scratch, lpart
 // [L, N, LP] sumsq partials of the L loss layers, lcoef [L] fp32 coefficient / numel, done u8 [N],
@@ -1799,6 +1878,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lap_split", &lap_split, "Laplacian pyramid split: lo / hi levels + sum-of-squares partials", py::arg("x"),
         py::arg("lo"), py::arg("hi"), py::arg("hpart"), py::arg("lpart"));
   m.def("lap_parts", &lap_parts, "partials per image of an H x W pyramid level", py::arg("H"), py::arg("W"));
+  m.def("occlusion_parts", &occlusion_parts, "max |heat| partials per (image, filter) of an S x S map", py::arg("S"));
+  m.def("occlude_variants", &occlude_variants, "the P + 1 occluded variants of each image of x0", py::arg("x0"),
+        py::arg("xv"), py::arg("patch"), py::arg("stride"));
+  m.def("occlusion_heat", &occlusion_heat, "per-pixel mean score drop of 4 filters + max |heat| partials",
+        py::arg("scores"), py::arg("idx"), py::arg("heat"), py::arg("part"), py::arg("patch"), py::arg("stride"));
+  m.def("occlusion_overlay", &occlusion_overlay, "2 x 2 u8 mosaic of the heat maps blended over the image",
+        py::arg("heat"), py::arg("part"), py::arg("idx"), py::arg("x0"), py::arg("out"));
   m.def("lap_merge", &lap_merge, "Laplacian pyramid merge with explicit or partial-derived per-image scales",
         py::arg("lo_n"), py::arg("hi"), py::arg("merged"), py::arg("out"), py::arg("scales") = py::none(),
         py::arg("hpart") = std::vector<Tensor>(), py::arg("lpart") = py::none(), py::arg("eps") = 1e-10);

@@ -295,6 +295,28 @@ int lap_split_launch(const void* x, int src, float* lo, float* hi, float* hpart,
 int lap_merge_launch(const float* prev, const float* hi, void* out, int dst, const float* scales, int S, int si,
                      const float* hpart, int hparts, const float* ppart, int pparts, float eps, int first, int N, int H,
                      int W, hipStream_t s);
+// Occlusion sensitivity (occlusion.hip; Zeiler & Fergus section 4.2). A p x p patch slides over an S x S image with
+// stride s: per axis g = ceil((S - p) / s) + 1 positions o_i = min(i s, S - p), P = g^2 patches. Valid geometry:
+// 16 <= S <= 4096, 8 <= p <= S / 2, 4 <= s <= p, P <= 255; every launcher returns -1 outside it.
+// OCC_PIX pixels per block (one per thread), one max|heat| partial per block: parts = occ_parts(S).
+constexpr int OCC_PIX = 256, OCC_RUN = 16, OCC_MAX_P = 255;
+inline int occ_parts(int S) { return (S * S + OCC_PIX - 1) / OCC_PIX; }
+inline int occ_grid(int S, int p, int s) {  // g, or -1 outside the definition
+  if (S < 16 || S > 4096 || p < 8 || 2 * p > S || s < 4 || s > p) return -1;
+  const int g = (S - p + s - 1) / s + 1;
+  return g * g <= OCC_MAX_P ? g : -1;
+}
+// xv [B (P + 1), S, S, 8] 16-bit: variant 0 = x0 [B, S, S, 8], variant 1 + i g + j = x0 with all 8 channels zero on
+// rows o_i .. o_i + p - 1, columns o_j .. o_j + p - 1
+int occlude_variants_launch(const uint16_t* x0, uint16_t* xv, int B, int S, int p, int s, hipStream_t st);
+// heat [B, 4, S, S] fp32 = mean over the covering patches of scores[b, 0, f] - scores[b, 1 + i g + j, f], f = idx[b, k]
+// (scores [B, P + 1, C] fp32, idx [B, 4] int32; f outside 0 .. C - 1: zero map); part [B, 4, parts] = block max |heat|
+int occlusion_heat_launch(const float* scores, const int* idx, float* heat, float* part, int B, int C, int S, int p,
+                          int s, hipStream_t st);
+// out u8 [B, 2 S, 2 S, 3]: tile k at [[0, 1], [2, 3]] = x0 + mean colour blended with red (heat >= 0) / blue by
+// 0.6 |heat| / max |heat[b, k]|; black where idx[b, k] < 0
+int occlusion_overlay_launch(const float* heat, const float* part, const int* idx, const uint16_t* x0, uint8_t* out,
+                             int B, int S, int dtype, hipStream_t st);
 // tiled DeepDream step: rolled tile gather -> owned-pixel pack (+ unit loss / sum|g| tail) ->
 // [all-gather of packs over ranks] -> update of the fp32 image straight from the packs
 int tile_gather_launch(const float* x, uint16_t* xin, const int* plan, const int* shift, int units, int rank, int world,

@@ -80,6 +80,8 @@ class RemoteService(_Remote):
         # GPU JPEG decode is the OWNER's switch: a front end sends coefficient frames only to an owner that
         # said it takes them
         self.gpu_decode = bool(info.get("gpu_jpeg_decode", False))
+        self.has_occlusion = bool(info.get("occlusion", False))  # likewise: OCCLUSION frames only to an owner that takes them
+        self.image_size = cfg.image_size
         self.codec = CodecPool(cfg.codec_workers)
 
     def layer_names(self):
@@ -106,6 +108,26 @@ class RemoteService(_Remote):
 
         async def send(cb):
             await loop.run_in_executor(self.codec.ex, self._decode_send, uri, layer, cb)
+
+        return await self._request(send, raw=True)
+
+    def _decode_send_occlusion(self, uri: str, layer: str, patch: int, stride: int, cb) -> None:
+        t0 = time.perf_counter()
+        img = read_data_url(uri)  # pixels, like DECONV: ImageDecodeError -> 400 in the app
+        self.client.send(ingest.OCCLUSION, cb, layer, img.shape[0], img.shape[1],
+                         (ingest.OCC_HEAD.pack(patch, stride), img), decode_s=time.perf_counter() - t0)
+
+    async def occlusion(self, uri: str, layer: str, patch: int = 32, stride: int = 16) -> str:
+        from ..ops.occlusion import occlusion_grid
+
+        self.validate_layer(layer)
+        occlusion_grid(self.image_size, patch, stride)  # ValueError -> 400 before anything is decoded or sent
+        if not self.has_occlusion:
+            raise RemoteError(400, "the GPU owner does not serve /occlusion")
+        loop = asyncio.get_running_loop()
+
+        async def send(cb):
+            await loop.run_in_executor(self.codec.ex, self._decode_send_occlusion, uri, layer, patch, stride, cb)
 
         return await self._request(send, raw=True)
 

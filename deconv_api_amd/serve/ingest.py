@@ -24,7 +24,9 @@ kinds: DECONV (payload = h*w*3 uint8 RGB pixels), STATUS / METRICS / LAYERS (no 
 text back), DREAM (payload = JSON header line + the data URL), DECONV_JPEG (GPU JPEG decode, sent only to
 an owner whose LAYERS reply says ``gpu_jpeg_decode``; payload = <B components, B kind, H 0> + the
 components' quantizers (uint16 [components][64]) + the int16 coefficients of codec.JpegCoeffs, whose
-count follows from h, w and kind). status: HTTP-like (200, 400, 503,
+count follows from h, w and kind), OCCLUSION (POST /occlusion; payload = <H patch, H stride> + h*w*3 uint8 RGB
+pixels, decoded in the front end like DECONV; sent only to an owner whose LAYERS reply says ``occlusion``). A kind
+the owner does not know is drained and answered 400; the connection stays up. status: HTTP-like (200, 400, 503,
 500); non-200 payloads are the error message. ``decode_us``: the front end's base64 + PIL decode time,
 recorded by the owner, whose /metrics therefore cover every front end of the rank.
 """
@@ -50,8 +52,9 @@ log = get_logger("deconv_api_amd.ingest")
 
 REQ = struct.Struct("<IBBHIIQI")
 RESP = struct.Struct("<IHQ")
-DECONV, STATUS, METRICS, LAYERS, DREAM, DECONV_JPEG = 1, 2, 3, 4, 5, 6
+DECONV, STATUS, METRICS, LAYERS, DREAM, DECONV_JPEG, OCCLUSION = 1, 2, 3, 4, 5, 6, 7
 JPEG_HEAD = struct.Struct("<BBH")
+OCC_HEAD = struct.Struct("<HH")
 SOCK_BUF = 8 << 20
 MAX_DREAM_BODY = 256 << 20  # JSON header + data URL (+ the guide's data URL) of one /deepdream request
 
@@ -75,6 +78,14 @@ def _recv_into(sock: socket.socket, mv: memoryview) -> None:
         if k == 0:
             raise ConnectionError("peer closed")
         got += k
+
+
+def _drain(sock: socket.socket, n: int) -> None:
+    buf = memoryview(bytearray(min(n, 1 << 20)))
+    while n > 0:
+        k = min(n, len(buf))
+        _recv_into(sock, buf[:k])
+        n -= k
 
 
 def _tune(sock: socket.socket) -> None:
@@ -182,17 +193,33 @@ class IngestServer:
                     self.requests += 1
                     M.HOST_STAGE.observe(dec_us * 1e-6, stage="decode")
                     self._deconv(rid, layer, JpegCoeffs(h, w, ncomp, jkind, qt, coef), reply)
+                elif kind == OCCLUSION:
+                    if nbytes != OCC_HEAD.size + h * w * 3 or h * w > MAX_PIXELS:
+                        reply(rid, 400, b"pixel payload does not match its shape or exceeds DV_MAX_PIXELS")
+                        return
+                    patch, stride = OCC_HEAD.unpack(_recv_exact(c, OCC_HEAD.size))
+                    img = np.empty((h, w, 3), np.uint8)
+                    _recv_into(c, memoryview(img).cast("B"))
+                    self.requests += 1
+                    M.HOST_STAGE.observe(dec_us * 1e-6, stage="decode")
+                    self._deconv(rid, layer, img, reply, occ=(patch, stride))
                 elif kind == DREAM:
                     if nbytes > MAX_DREAM_BODY:
                         reply(rid, 413, b"dream request too large")
                         return
                     body = _recv_exact(c, nbytes)
                     self._dream(rid, body, reply)
-                else:
+                elif kind in (STATUS, METRICS, LAYERS):
                     if nbytes:  # info requests carry no payload
                         reply(rid, 400, b"unexpected payload")
                         return
                     reply(rid, *self._info(kind))
+                else:  # a kind of a newer front end: skip its payload, keep the connection
+                    if nbytes > MAX_DREAM_BODY:
+                        reply(rid, 400, b"unknown request kind")
+                        return
+                    _drain(c, nbytes)
+                    reply(rid, 400, b"unknown request kind")
         except (ConnectionError, OSError, struct.error):
             pass
         finally:
@@ -202,7 +229,7 @@ class IngestServer:
                 pass
 
     # ------------------------------------------------------------------ request kinds
-    def _deconv(self, rid: int, layer: str, img: np.ndarray, reply) -> None:
+    def _deconv(self, rid: int, layer: str, img: np.ndarray, reply, occ=None) -> None:
         def done(value, exc):
             if exc is None:
                 if isinstance(value, np.ndarray):  # CPU / PIL path: raw mosaic, encode here
@@ -214,7 +241,10 @@ class IngestServer:
                 reply(rid, _status_of(exc), str(exc).strip('"').encode())
 
         try:
-            self.svc.submit(layer, img, done)
+            if occ is not None:  # ValueError (patch / stride / a sharding runner) -> 400
+                self.svc.submit(layer, img, done, occ=occ)
+            else:
+                self.svc.submit(layer, img, done)
         except Exception as e:  # noqa: BLE001 - unknown layer, queue full: answered at once
             done(None, e)
 
@@ -281,6 +311,8 @@ class IngestServer:
                 info = {"layers": self.svc.layer_names(), "names": list(self.svc.engine.names)}
                 if getattr(self.svc, "gpu_decode", False):  # only an owner that takes DECONV_JPEG frames says so:
                     info["gpu_jpeg_decode"] = True          # with the switch off the reply is what it always was
+                if hasattr(self.svc, "validate_occlusion"):  # an owner that takes OCCLUSION frames
+                    info["occlusion"] = True
                 return 200, json.dumps(info).encode()
         except Exception as e:  # noqa: BLE001
             return 500, repr(e).encode()

@@ -33,6 +33,8 @@ from ..codec.image import JpegCoeffs, decode_path, gpu_data_urls, gpu_jpeg_fits
 from ..runtime.staging import GpuScans
 from ..config import Config
 from ..engine.deconvnet import DeconvNet, UnknownLayerError
+from ..engine.occlusion import DEFAULT_PATCH, DEFAULT_STRIDE, Occlusion
+from ..ops.occlusion import occlusion_grid
 from ..models.vgg16 import VGG16
 from ..utils import metrics as M
 from ..utils.faults import FaultInjector
@@ -61,6 +63,7 @@ class _Job:
     t_launch: float = 0.0
     t_gpu: float = 0.0
     t_enc: float = 0.0
+    occ: Optional[tuple] = None  # (patch, stride): an occlusion request (POST /occlusion); None: a deconv request
 
 
 def load_model(cfg: Config) -> VGG16:
@@ -147,22 +150,42 @@ class DeconvService:
     def layer_names(self) -> List[str]:
         return [s.name for s in self.engine.specs[1:]]
 
-    def submit(self, layer: str, img, deliver) -> _Job:
+    def validate_occlusion(self, layer: str, patch: int, stride: int) -> None:
+        """Everything an occlusion request can be refused for before any GPU work: UnknownLayerError, or
+        ValueError (patch / stride outside the definition of ops/occlusion.py, a rank-0 sharding runner)."""
+        self.validate_layer(layer)
+        occlusion_grid(self.cfg.image_size, patch, stride)
+        if self.runner is not None:
+            raise ValueError("occlusion is served by a one-GPU owner")
+
+    def submit(self, layer: str, img, deliver, occ: Optional[tuple] = None) -> _Job:
         """Enqueue an already decoded HxWx3 uint8 image (or, with ``gpu_decode``, a JpegCoeffs);
         ``deliver(value, exc)`` is called from a service thread with the response string (or the
-        error). Raises at once for an unknown layer or a full queue."""
+        error). Raises at once for an unknown layer or a full queue. ``occ`` = (patch, stride): an
+        occlusion request, which runs as its own engine call, never grouped with other requests."""
         self.validate_layer(layer)
+        if occ is not None:
+            self.validate_occlusion(layer, *occ)
         if isinstance(img, JpegCoeffs) and not self.gpu_decode:
             raise ValueError("this service does not take JPEG coefficients (DV_GPU_JPEG_DECODE is off)")
         if self.q.qsize() >= self.cfg.max_queue:
             raise ServiceOverloaded("request queue is full")
-        job = _Job(layer, img, deliver)
+        job = _Job(layer, img, deliver, occ=occ)
         self.q.put(job)
         M.QUEUE_DEPTH.set(self.q.qsize())
         return job
 
     async def deconv(self, uri: str, layer: str) -> str:
         """The reference's POST / pipeline for one request -> data URL string."""
+        return await self._request(uri, layer, None)
+
+    async def occlusion(self, uri: str, layer: str, patch: int = DEFAULT_PATCH, stride: int = DEFAULT_STRIDE) -> str:
+        """POST /occlusion for one request -> data URL string of the occlusion-sensitivity mosaic (same queue, worker,
+        staging ring, copy-back and encoder as ``deconv``)."""
+        self.validate_occlusion(layer, patch, stride)
+        return await self._request(uri, layer, (patch, stride))
+
+    async def _request(self, uri: str, layer: str, occ: Optional[tuple]) -> str:
         self.validate_layer(layer)
         if self.q.qsize() >= self.cfg.max_queue:
             raise ServiceOverloaded("request queue is full")
@@ -173,7 +196,7 @@ class DeconvService:
         M.DECODE_PATH.inc(path=decode_path(uri, img, self.gpu_decode))
         fut = loop.create_future()
         job = self.submit(layer, img, lambda v, e: _deliver(loop, _set_exc if e is not None else _set_result,
-                                                            fut, e if e is not None else v))
+                                                            fut, e if e is not None else v), occ)
         res = await asyncio.wait_for(fut, timeout=self.cfg.request_timeout_s)
         if self.trace is not None:  # per-request stage timestamps (tools/latency.py --trace)
             self.trace.append((t0, job.t_enq, job.t_launch, job.t_gpu, job.t_enc, time.perf_counter()))
@@ -264,14 +287,17 @@ class DeconvService:
             last_beat = time.perf_counter()
             M.QUEUE_DEPTH.set(self.q.qsize())
             by_layer = {}
-            for j in jobs:
-                by_layer.setdefault(j.layer, []).append(j)
-            for layer, group in by_layer.items():
+            for n, j in enumerate(jobs):  # an occlusion job is a group of its own
+                by_layer.setdefault((j.layer, None if j.occ is None else n), []).append(j)
+            for (layer, _), group in by_layer.items():
                 t0 = time.perf_counter()
                 self._batch_t0 = t0
                 try:
                     for j in group:
                         j.t_launch = t0
+                    if group[0].occ is not None:
+                        self.done_q.put((self.launch_occlusion(layer, group[0].image, *group[0].occ), group, layer, t0))
+                        continue
                     if self.runner is not None:
                         b = self.runner.launch(layer, [j.image for j in group])
                         if inflight is not None:
@@ -390,9 +416,29 @@ class DeconvService:
             x = torch.empty(n, S, S, 8, dtype=self.engine.rt.dtype, device=self.device)
             st = self.ring.stage(images, x)
             res = self.engine.run(x, layer, k=self.cfg.filters, mode=self.cfg.mode)
-        if self.cfg.gpu_jpeg and gpu_jpeg_fits(res.mosaic.shape[2]):  # JPEG on the device: only scans cross PCIe
-            return ("staged", self.ring.copy_back_jpeg(st, res.mosaic, self.cfg.jpeg_quality))
-        return ("staged", self.ring.copy_back(st, res.mosaic))
+        return self._copy_back(st, res.mosaic)
+
+    def _copy_back(self, st, mosaic):
+        if self.cfg.gpu_jpeg and gpu_jpeg_fits(mosaic.shape[2]):  # JPEG on the device: only scans cross PCIe
+            return ("staged", self.ring.copy_back_jpeg(st, mosaic, self.cfg.jpeg_quality))
+        return ("staged", self.ring.copy_back(st, mosaic))
+
+    def launch_occlusion(self, layer: str, image, patch: int = DEFAULT_PATCH, stride: int = DEFAULT_STRIDE):
+        """Enqueue one occlusion request (engine/occlusion.py: the image's P + 1 variants as one eager forward);
+        returns a handle for ``finish_batch`` like ``launch_batch``."""
+        self.validate_occlusion(layer, patch, stride)
+        self.faults.on_batch()
+        occ = Occlusion(self.engine)
+        if self.ring is None:  # CPU
+            return ("host", occ.run(self.preprocess([image]), layer, patch, stride).mosaic.numpy())
+        S = self.cfg.image_size
+        x = torch.empty(1, S, S, 8, dtype=self.engine.rt.dtype, device=self.device)
+        st = self.ring.stage([image], x)
+        return self._copy_back(st, occ.run(x, layer, patch, stride).mosaic)
+
+    def run_occlusion(self, layer: str, image, patch: int = DEFAULT_PATCH, stride: int = DEFAULT_STRIDE) -> np.ndarray:
+        """Synchronous occlusion request (tests / tools / the CLI)."""
+        return self.finish_batch(self.launch_occlusion(layer, image, patch, stride))
 
     def finish_batch(self, handle) -> np.ndarray:
         if handle[0] == "host":
