@@ -1,5 +1,5 @@
 """Helpers shared by the exact-oracle GPU tests (test_conv_exact_gpu.py, test_conv_routes_exact_gpu.py,
-test_dream_exact_gpu.py): seeded
+test_dream_exact_gpu.py, test_engine_exact_gpu.py through engine_oracle.py): seeded
 integer operands, the method's conditions on a CPU reference, and bit equality with it. A plain module,
 not a conftest: nothing here changes how the suite is collected or run."""
 import pytest

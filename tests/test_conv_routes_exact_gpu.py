@@ -1,7 +1,8 @@
 """GPU: the conv kernels test_conv_exact_gpu.py leaves out, against the same EXACT oracle: the register-staged
 implicit GEMM (csrc/conv_igemm.hip), the 64-channel halo / row-streaming kernels (csrc/conv_smalln.hip), the
 halo-stream kernels' plain epilogues (csrc/conv_halo_stream.hip), the persistent 1x1 kernel (csrc/conv_pw.hip),
-the LDS-DMA kernel's 16-wide tiles and the grouped launches (csrc/conv_dma_group.hip).
+the LDS-DMA kernel's 16-wide tiles, the grouped launches (csrc/conv_dma_group.hip) and the classifier head's
+[M, 1, 1, K] GEMMs on the planner's automatic tile and split-K (section 9).
 
 The method is test_conv_exact_gpu.py's: operands are small integers (x in [-3, 3], weights in [-2, 2] thinned
 to about 96 taps, bias / residual / base in [-4, 4], masks from {-1, -0.0, 0, 1}), so every partial sum is an
@@ -137,9 +138,11 @@ def _untouched(buf, shape, left):
     return bool((chk == SENT).all())
 
 
-def _launch(c, policy="auto", x_extra=0, left=0, right=8, mask_extra=0, **extra_kw):
+def _launch(c, policy="auto", x_extra=0, left=0, right=8, mask_extra=0, x_fill=3.0, x_tail=False, **extra_kw):
     """Run case ``c`` on the GPU under ``policy``: x (and its mask) as channel slices of buffers ``x_extra`` /
-    ``mask_extra`` wider, the output through a sentinel-framed view. Returns (result, route, bits_flags)."""
+    ``mask_extra`` wider (x's extra channels hold ``x_fill``), the output through a sentinel-framed view.
+    ``x_tail``: x is the last rows of a longer dense buffer, so it ends where the storage ends.
+    Returns (result, route, bits_flags)."""
     dt = c.dt
     kw = dict(c.kw)
     if "code" in kw:
@@ -153,8 +156,14 @@ def _launch(c, policy="auto", x_extra=0, left=0, right=8, mask_extra=0, **extra_
     if c.base is not None:
         view.copy_(_dev(c.base, c.odt))
         kw["accumulate"] = True
+    if x_tail:
+        xbuf = torch.full((c.x.shape[0] + 3,) + tuple(c.x.shape[1:]), 3.0, dtype=dt, device=DEV)
+        xbuf[3:] = _dev(c.x, dt)
+        xd = xbuf[3:]
+    else:
+        xd = _wide(c.x, dt, x_extra, fill=x_fill)
     with _policy(policy):
-        got = ops.conv2d(_wide(c.x, dt, x_extra), c.cw.to_device(DEV, dt), out=view, **kw, **extra_kw)
+        got = ops.conv2d(xd, c.cw.to_device(DEV, dt), out=view, **kw, **extra_kw)
         r, bits = _route(), Cm.bits_flags()
     assert _untouched(buf, oshape, left), "wrote outside the output view"
     return got, r, bits
@@ -767,6 +776,100 @@ def test_dma_groups(native_lib, name, n, dt):
 
 
 # ----------------------------------------------------------------------------------------
+# 9. the classifier head's GEMMs: [M, 1, 1, K] rows on the LDS-DMA kernel, automatic tile and split-K
+# ----------------------------------------------------------------------------------------
+# VGG16Runtime packs fc1 / fc2 / predictions as 1x1 ConvWeights (models/vgg16.py); the engine runs them with
+# M = B rows going up and M = B K_filters rows coming down (engine/deconvnet.py _dense_up, backward). The planner
+# (csrc/conv_dma_plan.h auto_cfg, splitk) gives M OCpad <= 3e6 the 64 x 64 st3 tile and, up to small_splitk_mn =
+# 300 000, split-K 2 (16..19 K tiles) or 4 (>= 20); neither rule reads the CU count. Nothing is forced here.
+
+def _dn(seed, M, K, OC, **kw):
+    return dict(seed=seed, N=M, H=1, W=1, C=K, OC=OC, k=(1, 1), **kw)
+
+
+_DOWN = dict(bias=False, epi="f32")
+DENSE = {
+    # name: (case arguments without the dtype, route)
+    # fc1 / fc2 up: bias + ReLU, 16-bit. K = 1344 is 21 K tiles: split-K 4 with parts of 6, 5, 5, 5
+    **{f"up_m{M}_k{K}": (_dn(900 + M + K, M, K, 192), "dma 64x64 st3 ks4") for M in (1, 3, 4) for K in (1344, 4096)},
+    # predictions up: fp32 logits, no ReLU, OC 1000 < OCpad 1024: bias and columns past 1000 untouched
+    **{f"pred_up_m{M}": (_dn(910 + M, M, 4096, 1000, epi="f32", relu=False), "dma 64x64 st3 ks4") for M in (1, 5)},
+    # predictions down: K = 1000 -> Kpad 1024, 16 K tiles: split-K 2, the K tail inside every row
+    **{f"pred_down_m{M}_relu{int(r)}": (_dn(920 + M + r, M, 1000, 4096, relu=r, **_DOWN), "dma 64x64 st3 ks2")
+       for M in (4, 12) for r in (True, False)},
+    "fc_down_m12": (_dn(930, 12, 4096, 256, **_DOWN), "dma 64x64 st3 ks4"),
+    # the batch-size flips: M OCpad either side of small_splitk_mn (split-K 4 -> none) ...
+    "flip_splitk_below": (_dn(940, 73, 1344, 4096, **_DOWN), "dma 64x64 st3 ks4"),
+    "flip_splitk_above": (_dn(941, 74, 1344, 4096, **_DOWN), "dma 64x64 st3 ks1"),
+    # ... and of auto_cfg's 3 000 000 (the 64 x 64 tile -> 128 x 128; K = 256 is 4 K tiles: no split-K)
+    "flip_tile_below": (_dn(942, 119, 256, 25088, **_DOWN), "dma 64x64 st3 ks1"),
+    "flip_tile_above": (_dn(943, 128, 256, 25088, **_DOWN), "dma 128x128 st2 ks1"),
+}
+# the real fc1 shapes, bf16 only: name -> (M, K, OC, keep 1 weight in ``thin``, route). fc1.down's 102 760 448
+# weights put B's row offsets past 2^27 elements; its M OCpad = 401 408 is past small_splitk_mn: no split-K
+DENSE_REAL = {"fc1_up": (4, 25088, 4096, 256, "dma 64x64 st3 ks4"), "fc1_down": (16, 4096, 25088, 42, "dma 64x64 st3 ks1")}
+
+
+def _dense_plan(M, K, OC):
+    """(tile id, split-K) of csrc/conv_dma_plan.h auto_cfg / splitk for an unmasked 1x1 problem with K < 4096 or
+    M OCpad <= 3e6 (the cases of this section), independent of the CU count."""
+    ocp, kpad = Cm.oc_pad(OC), -(-K // 64) * 64
+    mn, nk = M * ocp, kpad // 64
+    if ocp % 64 == 0 and OC > 16 and mn <= 3_000_000:
+        return 8, (1 if mn > 300_000 else (4 if nk >= 20 else (2 if nk >= 16 else 1)))
+    assert ocp % 128 == 0 and OC > 64 and kpad < 1024 and nk < 8
+    return 3, 1
+
+
+@gpu
+@pytest.mark.parametrize("dt", [BF, HF], ids=["bf16", "fp16"])
+@pytest.mark.parametrize("name", sorted(DENSE))
+def test_dense_head_gemm(native_lib, name, dt):
+    """The dense head's GEMM shapes, bit for bit against the fp32 CPU conv, on the planner's own route: 1 to 128
+    rows on a 64-row tile, split-K 4 with unequal parts, OC < OCpad, a K tail inside each row (the padded k read
+    as zero although NaNs follow each row), both sides of the two batch-size route flips."""
+    args, want = DENSE[name]
+    c = _case(**args, dt=dt)
+    tail = args["C"] % 64 != 0
+    got, r, _ = _launch(c, "auto", x_extra=24 if tail else 0, x_fill=float("nan"))
+    assert r == want, r
+    _expect(c, got)
+    if tail:  # and with the rows ending where the allocation ends
+        got, r, _ = _launch(c, "auto", x_tail=True)
+        assert r == want, r
+        _expect(c, got)
+
+
+def _dense_real(name):
+    """A real fc1 shape on integer operands: weights in [-2, 2] drawn with one call (a table lookup of one
+    randint: 1 value in ``thin`` is non-zero, about 96 taps per output), its fp32 CPU reference and conditions."""
+    M, K, OC, thin, _ = DENSE_REAL[name]
+    g = _gen(950 + M)
+    x = _ints(g, (M, 1, 1, K), -3, 3)
+    lut = torch.zeros(4 * thin)
+    lut[:4] = torch.tensor([-2.0, -1.0, 1.0, 2.0])
+    w = lut[torch.randint(0, 4 * thin, (OC, K, 1, 1), generator=g, dtype=torch.int16).long()]
+    up = name == "fc1_up"
+    cw = Cm.ConvWeights(w, _ints(g, (OC,), -4, 4) if up else None, "fwd")
+    kw = dict(pad=(0, 0), relu=True, epilogue="bf16" if up else "f32", use_bias=up)
+    ref = ops.conv2d(x, cw, **kw)
+    _check_exact(ref, BF if up else F32, x, cw, 4.0, pad=(0, 0))
+    return types.SimpleNamespace(x=x, cw=cw, kw=kw, more={}, base=None, ref=ref, dt=BF, odt=BF if up else F32, OC=OC,
+                                 C=K, N=M, epi=kw["epilogue"])
+
+
+@gpu
+@pytest.mark.parametrize("name", sorted(DENSE_REAL))
+def test_dense_head_real_shapes(native_lib, name):
+    """fc1.up (M 4, K 25088, OC 4096: 392 K tiles in four parts) and fc1.down (M 16, K 4096, OC 25088: a 205 MB
+    B matrix) once each in bf16."""
+    c = _dense_real(name)
+    got, r, _ = _launch(c, "auto")
+    assert r == DENSE_REAL[name][4], r
+    _expect(c, got)
+
+
+# ----------------------------------------------------------------------------------------
 # the method's conditions for every case above, without a GPU
 # ----------------------------------------------------------------------------------------
 
@@ -794,6 +897,8 @@ def _all_case_args(G):
     for _, probs in GROUPS.values():
         for p in probs:
             yield from (dict(p, dt=dt) for dt in (BF, HF))
+    for args, _ in DENSE.values():
+        yield from (dict(args, dt=dt) for dt in (BF, HF))
 
 
 def test_conditions():
@@ -824,3 +929,14 @@ def test_conditions():
             oh, ow = p.get("out_hw", (p["H"], p["W"]))
             assert p["N"] * oh * ow * Cm.oc_pad(p["OC"]) <= 3_000_000 and p["OC"] > 16
     assert any(p["C"] % 64 for p in GROUPS["unaligned"][1])
+    # the dense head: every asserted route is the planner's rule for the shape, the two flips really flip, and the
+    # real shapes' partial sums are exact whatever the draw (|x| <= 3, |w| <= 2, |bias| <= 4)
+    for name, (args, want) in DENSE.items():
+        tile, ks = _dense_plan(args["N"], args["C"], args["OC"])
+        assert want == f"dma {'64x64 st3' if tile == 8 else '128x128 st2'} ks{ks}", name
+    assert DENSE["flip_splitk_below"][1] != DENSE["flip_splitk_above"][1]
+    assert DENSE["flip_tile_below"][1] != DENSE["flip_tile_above"][1]
+    assert 73 * 4096 <= 300_000 < 74 * 4096 and 119 * 25088 <= 3_000_000 < 128 * 25088
+    for name, (M, K, OC, thin, want) in DENSE_REAL.items():
+        assert 6 * K + 4 < 2 ** 24 and 80 <= K / thin <= 112
+        assert want == f"dma 64x64 st3 ks{_dense_plan(M, K, OC)[1]}" and _dense_plan(M, K, OC)[0] == 8

@@ -7,7 +7,8 @@ reports. No C++ is involved, so the same script runs at any commit; two recordin
 are comparable byte for byte. ``tests/fixtures/conv_dma_routes.txt`` is such a recording; the CPU test
 of the LDS-DMA planner (tests/test_conv_dma_plan.py) replays its rows.
 
-Workloads: the VGG16 deconvnet to block5_conv3 at B = 1, 4, 256 (K = 4); one InceptionV3 DeepDream octave
+Workloads: the VGG16 deconvnet to block5_conv3 at B = 1, 4, 256 (K = 4) and, with the classifier head, to
+predictions at B = 1 and 256 (the dense layers as [M, 1, 1, K] GEMMs, M = B up, 4 B down); one InceptionV3 DeepDream octave
 at 299^2; one ResNet-50 DeepDream step on 512^2 fp16 tiles; the shapes of the GPU tests that assert the
 routes the models do not reach; a few launches under non-default knobs.
 
@@ -119,6 +120,21 @@ def vgg16(rec):
         torch.cuda.synchronize()
 
 
+def vgg16_dense(rec):
+    """The classifier head: fc1 / fc2 / predictions up at M = B rows and down at M = B K rows (H = W = 1)."""
+    from deconv_api_amd.engine.deconvnet import DeconvNet
+    from deconv_api_amd.models.vgg16 import VGG16
+
+    eng = DeconvNet(VGG16.random(0).build(DEV, torch.bfloat16))
+    g = torch.Generator(device=DEV).manual_seed(2)
+    for B in (1, 256):
+        rec.section = f"vgg16 deconvnet predictions B={B} K=4"
+        x = torch.zeros(B, 224, 224, 8, dtype=torch.bfloat16, device=DEV)
+        x[..., :3] = (torch.rand(B, 224, 224, 3, device=DEV, generator=g) * 255 - 115).to(torch.bfloat16)
+        eng.run(x, "predictions", k=4)
+        torch.cuda.synchronize()
+
+
 def dream(rec):
     from deconv_api_amd.engine.deepdream import (RESNET_LAYERS, DeepDream, DreamSettings, TiledDeepDream,
                                                  inception_preprocess)
@@ -225,12 +241,12 @@ def route_test_shapes(rec):
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--out", required=True)
-    ap.add_argument("--only", default="", help="comma list of vgg16, dream, tests (default: all)")
+    ap.add_argument("--only", default="", help="comma list of vgg16, dense, dream, tests (default: all)")
     a = ap.parse_args(argv)
     rec = Recorder(ops.native.load())
     ops.native._mod = rec
     only = set(filter(None, a.only.split(",")))
-    for name, fn in (("vgg16", vgg16), ("dream", dream), ("tests", route_test_shapes)):
+    for name, fn in (("vgg16", vgg16), ("dense", vgg16_dense), ("dream", dream), ("tests", route_test_shapes)):
         if not only or name in only:
             fn(rec)
     ops.conv.check_stream_k()
