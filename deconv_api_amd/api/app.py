@@ -10,7 +10,8 @@
 
 Extensions: GET /ready (per-device status), GET /metrics (Prometheus text), GET /layers,
 POST /deepdream (when the DeepDream engine is available), POST /occlusion (occlusion sensitivity maps of the
-filters POST / reconstructs; engine/occlusion.py).
+filters POST / reconstructs; engine/occlusion.py), POST /activations (the feature maps of the same filters laid over
+the image; engine/activations.py; a layer without a feature map -> 400).
 
 Error handling differs deliberately from the reference (which 500s on all of these):
 missing fields -> 422 (FastAPI's own validation shape), undecodable image / malformed data URL /
@@ -57,6 +58,19 @@ _OCC_SCHEMA = {
                                            "layer": {"title": "Layer", "type": "string"},
                                            "patch": {"title": "Patch", "type": "integer", "default": 32},
                                            "stride": {"title": "Stride", "type": "integer", "default": 16}}}}
+            for ct in ("application/x-www-form-urlencoded", "multipart/form-data")
+        },
+    }
+}
+
+
+_ACT_SCHEMA = {
+    "requestBody": {
+        "required": True,
+        "content": {
+            ct: {"schema": {"title": "Body_activations_activations_post", "type": "object", "required": ["file", "layer"],
+                            "properties": {"file": {"title": "File", "type": "string"},
+                                           "layer": {"title": "Layer", "type": "string"}}}}
             for ct in ("application/x-www-form-urlencoded", "multipart/form-data")
         },
     }
@@ -216,6 +230,52 @@ def create_app(service=None, cfg: Optional[Config] = None, dream_service=None) -
         finally:
             M.REQUESTS.inc(route="/occlusion", status=status)
             M.LATENCY.observe(time.perf_counter() - t0, route="/occlusion", layer=layer)
+
+    @app.post("/activations", openapi_extra=_ACT_SCHEMA)
+    async def activations(request: Request):
+        """Extension (not in the reference): activation maps (Zeiler & Fergus figure 7 (b)) of the four filters
+        ``POST /`` would reconstruct: each filter's feature map, upsampled to the image and laid over it in red.
+        Form fields: file, layer (a conv or pool layer). The response has the shape of ``POST /``: the 2x2 mosaic
+        (true RGB) as a JPEG data URL."""
+        t0 = time.perf_counter()
+        status, layer = "200", "-"
+        try:
+            try:
+                form = parse_form(await request.body(), request.headers.get("content-type"))
+            except FormError as e:
+                status = "400"
+                return JSONResponse(status_code=400, content={"detail": str(e)})
+            missing = [f for f in ("file", "layer") if f not in form]
+            if missing:
+                status = "422"
+                return _missing(missing)
+            layer = form["layer"]
+            svc = get_service()
+            try:
+                url = await svc.activations(form["file"], layer)
+            except UnknownLayerError as e:
+                status = "400"
+                return JSONResponse(status_code=400, content={"detail": str(e).strip('"')})
+            except (ImageDecodeError, ValueError) as e:
+                status = "400"
+                return JSONResponse(status_code=400, content={"detail": str(e)})
+            except Exception as e:  # noqa: BLE001
+                from ..serve.service import ServiceOverloaded
+
+                code = getattr(e, "status", None)  # serve/frontend.py RemoteError: the GPU owner's answer
+                if isinstance(code, int) and code != 500:
+                    status = str(code)
+                    return JSONResponse(status_code=code, content={"detail": str(e)})
+                if isinstance(e, ServiceOverloaded):
+                    status = "503"
+                    return JSONResponse(status_code=503, content={"detail": str(e)})
+                status = "500"
+                log.exception("activations request failed")
+                return JSONResponse(status_code=500, content={"detail": "internal error"})
+            return _json_string_response(url)
+        finally:
+            M.REQUESTS.inc(route="/activations", status=status)
+            M.LATENCY.observe(time.perf_counter() - t0, route="/activations", layer=layer)
 
     @app.get("/ready")
     def ready():

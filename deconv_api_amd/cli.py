@@ -4,6 +4,7 @@
     python -m deconv_api_amd.cli dream photo.jpg --model inception_v3 --octaves 4 --steps 20 [--out-dir out/]
                                        [--guide other.jpg] [--lap-levels 4]
     python -m deconv_api_amd.cli occlusion photo.jpg --layer block5_conv3 [--patch 32 --stride 16] [--out-dir out/]
+    python -m deconv_api_amd.cli activations photo.jpg [more.png ...] --layer block5_conv3 [--out-dir out/]
     python -m deconv_api_amd.cli layers
 
 ``deconv`` writes ``<stem>_<layer>.jpg``: the 2x2 mosaic of the top-4 deconvnet reconstructions, the same
@@ -12,7 +13,9 @@ image ``POST /`` returns as a data URL (reference: app/main.py:45-78), all files
 that image's features (the route's ``guide`` field), with ``--lap-levels N`` the gradient of every step is
 Laplacian-pyramid normalised over N levels (the route's ``lap_levels`` field). ``occlusion`` writes
 ``<stem>_occlusion_<layer>.jpg``: the JPEG ``POST /occlusion`` returns (occlusion sensitivity maps of the same four
-filters, one image after another). Configuration as the server's
+filters, one image after another). ``activations`` writes ``<stem>_activations_<layer>.jpg``: the JPEG
+``POST /activations`` returns (the feature maps of the same four filters laid over the image), all files as one
+batch on the device. Configuration as the server's
 (``DV_*`` variables, config.py) with ``--device`` / ``--dtype`` / ``--weights`` overrides.
 """
 from __future__ import annotations
@@ -69,9 +72,10 @@ def cmd_deconv(a, cfg) -> int:
     return 0
 
 
-def _route_jpeg(svc, mos) -> bytes:
-    """The JPEG inside the data URL the service's routes answer with for the one-image result ``mos``: encoded the
-    way serve/service.py's ``_encode_deliver`` does (GPU scans, the native encoder's restart segments, or PIL)."""
+def _route_jpeg(svc, mos, b: int = 0) -> bytes:
+    """The JPEG inside the data URL the service's routes answer with for image ``b`` of the result ``mos`` as a
+    request of its own: encoded the way serve/service.py's ``_encode_deliver`` does (GPU scans, the native encoder's
+    restart segments, or PIL)."""
     import base64
     from urllib.parse import unquote
 
@@ -81,11 +85,11 @@ def _route_jpeg(svc, mos) -> bytes:
 
     q, th = svc.cfg.jpeg_quality, svc.cfg.encode_threads
     if isinstance(mos, GpuScans):
-        url = gpu_data_urls(mos.packed, mos.off, mos.H, mos.W, q, th)[0]
+        url = gpu_data_urls(mos.packed, mos.off, mos.H, mos.W, q, th)[b]
     elif svc.native_codec:
-        url = encode_data_urls(mos[:1], q, th)[0]
+        url = encode_data_urls(mos[b:b + 1], q, th)[0]
     else:
-        url = encode_data_url(mos[0], q)
+        url = encode_data_url(mos[b], q)
     if not isinstance(url, str):
         url = bytes(url).decode("ascii")
     return base64.b64decode(unquote(url.split(",", 1)[1]))
@@ -106,6 +110,24 @@ def cmd_occlusion(a, cfg) -> int:
         dst = os.path.join(a.out_dir, f"{_stem(p)}_occlusion_{a.layer}.jpg")
         with open(dst, "wb") as f:
             f.write(jpeg)
+        print(dst)
+    return 0
+
+
+def cmd_activations(a, cfg) -> int:
+    from .serve.service import DeconvService
+
+    svc = DeconvService(cfg)
+    try:
+        svc.validate_activations(a.layer)  # fails before any decode or compute
+        mos = svc.run_activations(a.layer, _read(a.images))
+    finally:
+        svc.close()
+    os.makedirs(a.out_dir, exist_ok=True)
+    for b, p in enumerate(a.images):
+        dst = os.path.join(a.out_dir, f"{_stem(p)}_activations_{a.layer}.jpg")
+        with open(dst, "wb") as f:
+            f.write(_route_jpeg(svc, mos, b))
         print(dst)
     return 0
 
@@ -166,6 +188,10 @@ def main(argv=None) -> int:
     o.add_argument("--patch", type=int, default=32, help="side of the grey square (8 .. half the image side)")
     o.add_argument("--stride", type=int, default=16, help="step of the square (4 .. patch)")
     o.add_argument("--out-dir", default=".")
+    v = sub.add_parser("activations", help="activation-map mosaic of each image")
+    v.add_argument("images", nargs="+")
+    v.add_argument("--layer", default="block5_conv3")
+    v.add_argument("--out-dir", default=".")
     sub.add_parser("layers", help="the VGG16 layer names POST / accepts")
     a = ap.parse_args(argv)
 
@@ -179,7 +205,8 @@ def main(argv=None) -> int:
     from .engine.deconvnet import UnknownLayerError
 
     try:
-        return {"deconv": cmd_deconv, "dream": cmd_dream, "occlusion": cmd_occlusion, "layers": cmd_layers}[a.cmd](a, cfg)
+        return {"deconv": cmd_deconv, "dream": cmd_dream, "occlusion": cmd_occlusion, "activations": cmd_activations,
+                "layers": cmd_layers}[a.cmd](a, cfg)
     except (UnknownLayerError, ImageDecodeError, ValueError, OSError) as e:  # the HTTP routes' 400s
         print(f"error: {str(e).strip(chr(34))}", file=sys.stderr)
         return 2

@@ -1018,6 +1018,29 @@ void occlusion_overlay(Tensor heat, Tensor part, Tensor idx, Tensor x0, Tensor o
            "occlusion_overlay");
 }
 
+// Activation maps (actmap.hip): act [B, H, W, C] 16-bit, idx [B, 4] -> heat [B, 4, S, S], part [B, 4, parts]
+void activation_heat(Tensor act, Tensor idx, Tensor heat, Tensor part) {
+  check_cuda(act, "activation_heat: act");
+  check_cuda(heat, "activation_heat: heat");
+  c10::hip::HIPGuardMasqueradingAsCUDA guard(act.device());
+  TORCH_CHECK(is16(act) && act.dim() == 4 && act.is_contiguous() && act.size(0) >= 1 && act.size(0) <= 65535 &&
+                  act.size(1) >= 1 && act.size(1) <= 4096 && act.size(2) >= 1 && act.size(2) <= 4096 &&
+                  act.size(3) >= 1 && act.size(1) * act.size(2) * act.size(3) <= 0x7FFFFFFFLL,
+              "activation_heat: act contiguous bf16 / fp16 [B, H, W, C], B <= 65535, H W C < 2^31");
+  TORCH_CHECK(heat.dim() == 4 && heat.size(1) == 4 && heat.size(2) == heat.size(3) && heat.size(2) >= 1 &&
+                  heat.size(2) <= 4096,
+              "activation_heat: heat [B, 4, S, S], S <= 4096");
+  const int64_t B = act.size(0), S = heat.size(2);
+  need(act, act.numel() * 2, "activation_heat: act");
+  occ_like(heat, act, at::kFloat, {B, 4, S, S}, "activation_heat: heat");
+  occ_like(idx, act, at::kInt, {B, 4}, "activation_heat: idx");
+  occ_like(part, act, at::kFloat, {B, 4, dv::occ_parts((int)S)}, "activation_heat: part");
+  check_rc(dv::activation_heat_launch(reinterpret_cast<const uint16_t*>(act.data_ptr()), idx.data_ptr<int>(),
+                                      heat.data_ptr<float>(), part.data_ptr<float>(), (int)B, (int)act.size(1),
+                                      (int)act.size(2), (int)act.size(3), (int)S, dt_of(act), cur_stream()),
+           "activation_heat");
+}
+
 // Fused DeepDream update (engine/deepdream.py): g [N,H,W,8] 16-bit input gradient, x [N,H,W,3] fp32
 // master image (updated in place), xin [N,H,W,8] next network input, gpart [N, P] scratch, lpart
 // [L, N, LP] sumsq partials of the L loss layers, lcoef [L] fp32 coefficient / numel, done u8 [N],
@@ -1885,6 +1908,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("scores"), py::arg("idx"), py::arg("heat"), py::arg("part"), py::arg("patch"), py::arg("stride"));
   m.def("occlusion_overlay", &occlusion_overlay, "2 x 2 u8 mosaic of the heat maps blended over the image",
         py::arg("heat"), py::arg("part"), py::arg("idx"), py::arg("x0"), py::arg("out"));
+  m.def("activation_heat", &activation_heat, "4 feature maps upsampled bilinearly to S x S + max |heat| partials",
+        py::arg("act"), py::arg("idx"), py::arg("heat"), py::arg("part"));
   m.def("lap_merge", &lap_merge, "Laplacian pyramid merge with explicit or partial-derived per-image scales",
         py::arg("lo_n"), py::arg("hi"), py::arg("merged"), py::arg("out"), py::arg("scales") = py::none(),
         py::arg("hpart") = std::vector<Tensor>(), py::arg("lpart") = py::none(), py::arg("eps") = 1e-10);

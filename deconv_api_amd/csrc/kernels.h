@@ -317,6 +317,12 @@ int occlusion_heat_launch(const float* scores, const int* idx, float* heat, floa
 // 0.6 |heat| / max |heat[b, k]|; black where idx[b, k] < 0
 int occlusion_overlay_launch(const float* heat, const float* part, const int* idx, const uint16_t* x0, uint8_t* out,
                              int B, int S, int dtype, hipStream_t st);
+// Activation maps (actmap.hip): heat [B, 4, S, S] fp32 = channel idx[b, k] of act [B, H, W, C] (16-bit NHWC) upsampled
+// bilinearly (half-pixel centres) by r = S / H; a filter outside 0 .. C - 1 gives a zero map; part [B, 4, occ_parts(S)] =
+// block max |heat|, the layout occlusion_overlay_launch consumes. Valid: 16 <= S <= 4096, H == W, r a power of two in
+// 1 .. 64, C % 8 == 0, H W C <= 2^31 - 1, 1 <= B <= 65535; -1 outside.
+int activation_heat_launch(const uint16_t* act, const int* idx, float* heat, float* part, int B, int H, int W, int C,
+                           int S, int dtype, hipStream_t st);
 // tiled DeepDream step: rolled tile gather -> owned-pixel pack (+ unit loss / sum|g| tail) ->
 // [all-gather of packs over ranks] -> update of the fp32 image straight from the packs
 int tile_gather_launch(const float* x, uint16_t* xin, const int* plan, const int* shift, int units, int rank, int world,

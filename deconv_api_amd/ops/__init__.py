@@ -7,6 +7,7 @@ from .misc import (CAFFE_MEAN, channel_sum, softmax_rows, deprocess_mosaic, maxp
 from .jpeg_dec import jpeg_coeffs_to_rgb
 from .lapnorm import lap_merge, lap_normalize, lap_split
 from .occlusion import occlude_variants, occlusion_grid, occlusion_heat, occlusion_overlay
+from .actmap import activation_heat
 from . import native
 
 __all__ = [
@@ -14,6 +15,6 @@ __all__ = [
     "unpool_ref", "CAFFE_MEAN", "channel_sum", "deprocess_mosaic", "maxpool2x2", "preprocess_ref",
     "resize_mode", "resize_preprocess", "resize_u8_ref", "seed_deconv3x3", "seed_map", "topk_positive", "unpool2x2",
     "softmax_rows", "jpeg_coeffs_to_rgb", "lap_split", "lap_merge", "lap_normalize",
-    "occlusion_grid", "occlude_variants", "occlusion_heat", "occlusion_overlay",
+    "occlusion_grid", "occlude_variants", "occlusion_heat", "occlusion_overlay", "activation_heat",
     "native",
 ]

@@ -81,6 +81,8 @@ class RemoteService(_Remote):
         # said it takes them
         self.gpu_decode = bool(info.get("gpu_jpeg_decode", False))
         self.has_occlusion = bool(info.get("occlusion", False))  # likewise: OCCLUSION frames only to an owner that takes them
+        # ACTIVATIONS frames only to an owner that announced the key, and only for the layers it lists
+        self.activation_layers = info.get("activations")
         self.image_size = cfg.image_size
         self.codec = CodecPool(cfg.codec_workers)
 
@@ -128,6 +130,25 @@ class RemoteService(_Remote):
 
         async def send(cb):
             await loop.run_in_executor(self.codec.ex, self._decode_send_occlusion, uri, layer, patch, stride, cb)
+
+        return await self._request(send, raw=True)
+
+    def _decode_send_activations(self, uri: str, layer: str, cb) -> None:
+        t0 = time.perf_counter()
+        img = read_data_url(uri)  # pixels, like DECONV: ImageDecodeError -> 400 in the app
+        self.client.send(ingest.ACTIVATIONS, cb, layer, img.shape[0], img.shape[1], img,
+                         decode_s=time.perf_counter() - t0)
+
+    async def activations(self, uri: str, layer: str) -> str:
+        self.validate_layer(layer)
+        if self.activation_layers is None:
+            raise RemoteError(400, "the GPU owner does not serve /activations")
+        if layer not in self.activation_layers:  # ValueError -> 400 before anything is decoded or sent
+            raise ValueError(f"layer {layer!r} has no feature map (activation maps take a conv or pool layer)")
+        loop = asyncio.get_running_loop()
+
+        async def send(cb):
+            await loop.run_in_executor(self.codec.ex, self._decode_send_activations, uri, layer, cb)
 
         return await self._request(send, raw=True)
 

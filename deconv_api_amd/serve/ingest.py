@@ -25,7 +25,9 @@ text back), DREAM (payload = JSON header line + the data URL), DECONV_JPEG (GPU 
 an owner whose LAYERS reply says ``gpu_jpeg_decode``; payload = <B components, B kind, H 0> + the
 components' quantizers (uint16 [components][64]) + the int16 coefficients of codec.JpegCoeffs, whose
 count follows from h, w and kind), OCCLUSION (POST /occlusion; payload = <H patch, H stride> + h*w*3 uint8 RGB
-pixels, decoded in the front end like DECONV; sent only to an owner whose LAYERS reply says ``occlusion``). A kind
+pixels, decoded in the front end like DECONV; sent only to an owner whose LAYERS reply says ``occlusion``),
+ACTIVATIONS (POST /activations; payload = the pixels, like DECONV; sent only to an owner whose LAYERS reply has
+``activations``, the names of the layers that have a feature map). A kind
 the owner does not know is drained and answered 400; the connection stays up. status: HTTP-like (200, 400, 503,
 500); non-200 payloads are the error message. ``decode_us``: the front end's base64 + PIL decode time,
 recorded by the owner, whose /metrics therefore cover every front end of the rank.
@@ -52,7 +54,7 @@ log = get_logger("deconv_api_amd.ingest")
 
 REQ = struct.Struct("<IBBHIIQI")
 RESP = struct.Struct("<IHQ")
-DECONV, STATUS, METRICS, LAYERS, DREAM, DECONV_JPEG, OCCLUSION = 1, 2, 3, 4, 5, 6, 7
+DECONV, STATUS, METRICS, LAYERS, DREAM, DECONV_JPEG, OCCLUSION, ACTIVATIONS = 1, 2, 3, 4, 5, 6, 7, 8
 JPEG_HEAD = struct.Struct("<BBH")
 OCC_HEAD = struct.Struct("<HH")
 SOCK_BUF = 8 << 20
@@ -161,7 +163,7 @@ class IngestServer:
             while not self._stop.is_set():
                 rid, kind, _, llen, h, w, nbytes, dec_us = REQ.unpack(_recv_exact(c, REQ.size))
                 layer = _recv_exact(c, llen).decode() if llen else ""
-                if kind == DECONV:
+                if kind in (DECONV, ACTIVATIONS):
                     if nbytes != h * w * 3 or h * w > MAX_PIXELS:
                         # the front ends enforce the same cap before decoding; a frame that breaks it is not
                         # worth draining (up to 2^64 bytes): answer and drop the connection
@@ -171,7 +173,7 @@ class IngestServer:
                     _recv_into(c, memoryview(img).cast("B"))
                     self.requests += 1
                     M.HOST_STAGE.observe(dec_us * 1e-6, stage="decode")
-                    self._deconv(rid, layer, img, reply)
+                    self._deconv(rid, layer, img, reply, act=kind == ACTIVATIONS)
                 elif kind == DECONV_JPEG:
                     # sizes are checked against the header BEFORE anything is received, as for DECONV
                     ncomp, jkind, _ = JPEG_HEAD.unpack(_recv_exact(c, JPEG_HEAD.size)) if nbytes >= JPEG_HEAD.size else (0, 0, 0)
@@ -229,7 +231,7 @@ class IngestServer:
                 pass
 
     # ------------------------------------------------------------------ request kinds
-    def _deconv(self, rid: int, layer: str, img: np.ndarray, reply, occ=None) -> None:
+    def _deconv(self, rid: int, layer: str, img: np.ndarray, reply, occ=None, act=False) -> None:
         def done(value, exc):
             if exc is None:
                 if isinstance(value, np.ndarray):  # CPU / PIL path: raw mosaic, encode here
@@ -243,6 +245,8 @@ class IngestServer:
         try:
             if occ is not None:  # ValueError (patch / stride / a sharding runner) -> 400
                 self.svc.submit(layer, img, done, occ=occ)
+            elif act:  # ValueError (a layer without a feature map / a sharding runner) -> 400
+                self.svc.submit(layer, img, done, act=True)
             else:
                 self.svc.submit(layer, img, done)
         except Exception as e:  # noqa: BLE001 - unknown layer, queue full: answered at once
@@ -313,6 +317,8 @@ class IngestServer:
                     info["gpu_jpeg_decode"] = True          # with the switch off the reply is what it always was
                 if hasattr(self.svc, "validate_occlusion"):  # an owner that takes OCCLUSION frames
                     info["occlusion"] = True
+                if hasattr(self.svc, "activation_layers"):  # an owner that takes ACTIVATIONS frames, for these layers
+                    info["activations"] = self.svc.activation_layers()
                 return 200, json.dumps(info).encode()
         except Exception as e:  # noqa: BLE001
             return 500, repr(e).encode()

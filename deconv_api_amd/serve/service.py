@@ -32,6 +32,7 @@ from ..codec import CodecPool, encode_data_url, encode_data_urls, read_data_url
 from ..codec.image import JpegCoeffs, decode_path, gpu_data_urls, gpu_jpeg_fits
 from ..runtime.staging import GpuScans
 from ..config import Config
+from ..engine.activations import ActivationMaps
 from ..engine.deconvnet import DeconvNet, UnknownLayerError
 from ..engine.occlusion import DEFAULT_PATCH, DEFAULT_STRIDE, Occlusion
 from ..ops.occlusion import occlusion_grid
@@ -64,6 +65,7 @@ class _Job:
     t_gpu: float = 0.0
     t_enc: float = 0.0
     occ: Optional[tuple] = None  # (patch, stride): an occlusion request (POST /occlusion); None: a deconv request
+    act: bool = False  # an activation-map request (POST /activations)
 
 
 def load_model(cfg: Config) -> VGG16:
@@ -158,19 +160,32 @@ class DeconvService:
         if self.runner is not None:
             raise ValueError("occlusion is served by a one-GPU owner")
 
-    def submit(self, layer: str, img, deliver, occ: Optional[tuple] = None) -> _Job:
+    def validate_activations(self, layer: str) -> None:
+        """Everything an activation-map request can be refused for before any GPU work: UnknownLayerError, or
+        ValueError (a flatten / dense layer has no feature map, a rank-0 sharding runner)."""
+        ActivationMaps(self.engine).check_layer(layer)
+        if self.runner is not None:
+            raise ValueError("activations are served by a one-GPU owner")
+
+    def activation_layers(self) -> List[str]:
+        return ActivationMaps(self.engine).spatial_layers()
+
+    def submit(self, layer: str, img, deliver, occ: Optional[tuple] = None, act: bool = False) -> _Job:
         """Enqueue an already decoded HxWx3 uint8 image (or, with ``gpu_decode``, a JpegCoeffs);
         ``deliver(value, exc)`` is called from a service thread with the response string (or the
         error). Raises at once for an unknown layer or a full queue. ``occ`` = (patch, stride): an
-        occlusion request, which runs as its own engine call, never grouped with other requests."""
+        occlusion request, which runs as its own engine call, never grouped with other requests. ``act``: an
+        activation-map request, grouped only with the other activation requests of its layer."""
         self.validate_layer(layer)
         if occ is not None:
             self.validate_occlusion(layer, *occ)
+        if act:
+            self.validate_activations(layer)
         if isinstance(img, JpegCoeffs) and not self.gpu_decode:
             raise ValueError("this service does not take JPEG coefficients (DV_GPU_JPEG_DECODE is off)")
         if self.q.qsize() >= self.cfg.max_queue:
             raise ServiceOverloaded("request queue is full")
-        job = _Job(layer, img, deliver, occ=occ)
+        job = _Job(layer, img, deliver, occ=occ, act=act)
         self.q.put(job)
         M.QUEUE_DEPTH.set(self.q.qsize())
         return job
@@ -185,7 +200,13 @@ class DeconvService:
         self.validate_occlusion(layer, patch, stride)
         return await self._request(uri, layer, (patch, stride))
 
-    async def _request(self, uri: str, layer: str, occ: Optional[tuple]) -> str:
+    async def activations(self, uri: str, layer: str) -> str:
+        """POST /activations for one request -> data URL string of the activation-map mosaic (same queue, worker,
+        staging ring, copy-back and encoder as ``deconv``; requests of one layer share one forward)."""
+        self.validate_activations(layer)
+        return await self._request(uri, layer, None, act=True)
+
+    async def _request(self, uri: str, layer: str, occ: Optional[tuple], act: bool = False) -> str:
         self.validate_layer(layer)
         if self.q.qsize() >= self.cfg.max_queue:
             raise ServiceOverloaded("request queue is full")
@@ -196,7 +217,7 @@ class DeconvService:
         M.DECODE_PATH.inc(path=decode_path(uri, img, self.gpu_decode))
         fut = loop.create_future()
         job = self.submit(layer, img, lambda v, e: _deliver(loop, _set_exc if e is not None else _set_result,
-                                                            fut, e if e is not None else v), occ)
+                                                            fut, e if e is not None else v), occ, act)
         res = await asyncio.wait_for(fut, timeout=self.cfg.request_timeout_s)
         if self.trace is not None:  # per-request stage timestamps (tools/latency.py --trace)
             self.trace.append((t0, job.t_enq, job.t_launch, job.t_gpu, job.t_enc, time.perf_counter()))
@@ -287,8 +308,8 @@ class DeconvService:
             last_beat = time.perf_counter()
             M.QUEUE_DEPTH.set(self.q.qsize())
             by_layer = {}
-            for n, j in enumerate(jobs):  # an occlusion job is a group of its own
-                by_layer.setdefault((j.layer, None if j.occ is None else n), []).append(j)
+            for n, j in enumerate(jobs):  # an occlusion job is a group of its own, a layer's activation jobs are one
+                by_layer.setdefault((j.layer, "act" if j.act else None if j.occ is None else n), []).append(j)
             for (layer, _), group in by_layer.items():
                 t0 = time.perf_counter()
                 self._batch_t0 = t0
@@ -297,6 +318,9 @@ class DeconvService:
                         j.t_launch = t0
                     if group[0].occ is not None:
                         self.done_q.put((self.launch_occlusion(layer, group[0].image, *group[0].occ), group, layer, t0))
+                        continue
+                    if group[0].act:
+                        self.done_q.put((self.launch_activations(layer, [j.image for j in group]), group, layer, t0))
                         continue
                     if self.runner is not None:
                         b = self.runner.launch(layer, [j.image for j in group])
@@ -439,6 +463,24 @@ class DeconvService:
     def run_occlusion(self, layer: str, image, patch: int = DEFAULT_PATCH, stride: int = DEFAULT_STRIDE) -> np.ndarray:
         """Synchronous occlusion request (tests / tools / the CLI)."""
         return self.finish_batch(self.launch_occlusion(layer, image, patch, stride))
+
+    def launch_activations(self, layer: str, images: List[np.ndarray]):
+        """Enqueue the activation-map requests of one layer (engine/activations.py: one eager forward of all the
+        images); returns a handle for ``finish_batch`` like ``launch_batch``."""
+        self.validate_activations(layer)
+        self.faults.on_batch()
+        maps = ActivationMaps(self.engine)
+        n = len(images)
+        if self.ring is None:  # CPU
+            return ("host", maps.run(self.preprocess(images), layer).mosaic.numpy())
+        S = self.cfg.image_size
+        x = torch.empty(n, S, S, 8, dtype=self.engine.rt.dtype, device=self.device)
+        st = self.ring.stage(images, x)
+        return self._copy_back(st, maps.run(x, layer).mosaic)
+
+    def run_activations(self, layer: str, images: List[np.ndarray]) -> np.ndarray:
+        """Synchronous activation-map batch (tests / tools / the CLI)."""
+        return self.finish_batch(self.launch_activations(layer, images))
 
     def finish_batch(self, handle) -> np.ndarray:
         if handle[0] == "host":
