@@ -738,9 +738,16 @@ __device__ __forceinline__ void epi_tail(const ConvArgs& a, uint4 v, int grow, i
 // LDS-staged 16-bit epilogue. The MFMA C layout gives each lane 4 rows x 1 column per 16x16
 // block, i.e. 2-byte scattered stores; instead the tile is written to LDS (the freed operand
 // stages, 16-B chunks XOR-swizzled by row) and read back as 8-channel chunks: every global
-// store, residual load, emask load and accumulate load is one 16-B access. Semantics as
+// store, residual load, emask load and accumulate load is one 16-B access. ORDER of operations as
 // epilogue/epilogue_res: v = acc + bias, [ReLU] (before a += out), + res, [ReLU] (after a res
 // add), zeroed where emask <= 0. Stores of a row's last partial chunk (OC % 8) go per element.
+// ROUNDING differs from them: the tile in LDS is 16-bit (an fp32 tile does not fit the freed operand
+// stages at 256 x 256), so v is rounded to nearest even AFTER the first ReLU, and epi_combine / the
+// per-chunk loop / epi_tail add `out` and `res` to that rounded value in fp32 and round a second time
+// ('staged'). epilogue, epilogue_res and splitk_reduce_kernel round once, at the end ('single'); with
+// res or accumulate the two differ by one 16-bit ulp on about one output in eight. Without them there
+// is one rounding here too. docs/KERNELS.md "Rounding points"; tests/test_conv_rounding_exact_gpu.py
+// pins each route to its model.
 template <int DT, int NT, int BM, int BN, int FM, int FN>
 __device__ __forceinline__ void epilogue_lds(const ConvArgs& a, const f32x4 (&acc)[FM][FN], uint8_t* smem, int m0,
                                              int n0, int wm, int wn, int lane, int tid, bool writer) {
@@ -1170,8 +1177,10 @@ __global__ void __launch_bounds__(512) conv_dma_kw3_kernel(const ConvArgs a, int
 // Main loop: a fragment pipeline (the next kw sub-step's B fragments read into a second register
 // set, each A fragment register refilled with the next sub-step's fragment right after its 4
 // MFMAs; the order pinned by sched_group_barrier), so only a K step's first sub-step waits for LDS
-// reads. Numerics equal the LDS-staged epilogue (same fp32 ops, same rounding). Buffer parity
-// follows a global step counter (odd step counts per tile).
+// reads. Numerics equal the LDS-staged epilogue's PLAIN store (same fp32 ops, one round-to-nearest-
+// even conversion of relu(acc + bias)); this kernel takes no res / accumulate / emask, so the staged
+// epilogue's second rounding never arises here. Buffer parity follows a global step counter (odd step
+// counts per tile).
 // Measured (tools/kw3_ab.py, profiles/kw3_ab_r4.txt): 2-4 % faster per launch than KW3 on every
 // config-2 shape. Measured and removed: the fragment pipeline alone in the non-persistent kernel
 // (-2 % .. +2 %, noise) and the next step's DMA pieces issued one per MFMA group instead of all

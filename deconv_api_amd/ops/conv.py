@@ -279,6 +279,15 @@ def conv2d(x: torch.Tensor, cw: ConvWeights, *, stride: int = 1, pad=None, relu:
     (``accumulate``); ReLU (with ``res``); zero where ``emask`` <= 0 LAST, so with ``accumulate`` and
     ``emask`` the old output is masked too: out = (out + conv) * (emask > 0), the input gradient of a
     ReLU output summed over its consumers (ops/autograd.py dgrad_strided_into, ops/inception.py).
+    Rounding points (docs/KERNELS.md "Rounding points"; tests/test_conv_rounding_exact_gpu.py): every step above
+    is fp32 and a 16-bit output is rounded to nearest even. The CPU path, the register epilogues, the split-K
+    reduce and the register-staged kernel round ONCE, at the end ('single'). The LDS-staged epilogues (16-B
+    aligned out / res / emask rows on the LDS-DMA and KW3 kernels, the persistent 1x1 kernel) hold the tile in
+    16 bits: they round v after the first ReLU, add ``res`` / the old ``out`` to that rounded value in fp32 and
+    round again ('staged'), so with ``res`` or ``accumulate`` their result may differ from the CPU path's by one
+    16-bit ulp. Without ``res`` / ``accumulate`` the two coincide. The 'pool' epilogue rounds each value to the
+    output type BEFORE the window comparison: values and switch codes equal those of the unfused conv -> store
+    -> maxpool2x2.
     ``stats`` (GPU, fp32 epilogue): fp64 [N / stats_div, 2] receives {sum, sum of squares} of each
     group of ``stats_div`` output images (the single-pass mosaic deprocess consumes it).
     ``unpool_out``: switch codes [N / unpool_div, OH, OW, OC]; the result is max-unpooled in the
@@ -362,14 +371,25 @@ def _conv2d_ref(x, cw, N, H, W, C, OH, OW, OC, stride, pad, relu, relu_in, in_mo
         X = F.pad(X, (pad[1], rr, pad[0], rb))
         Y = F.conv2d(X, cw.w_oihw.float(), bias, stride=stride)
     y = Y.permute(0, 2, 3, 1)
-    if res is not None:
+
+    def act(t):
+        if relu and relu_cols > 0:
+            return torch.cat([t[..., :relu_cols].clamp_min(0), t[..., relu_cols:]], dim=-1)
+        return t.clamp_min(0) if relu else t
+
+    # the documented order (conv2d docstring), all in fp32 and rounded ONCE at the end: ReLU (without res);
+    # += res; += the old out; ReLU (with res); emask last
+    acc_out = accumulate and out is not None and epilogue != "pool"
+    if res is None:
+        y = act(y)
+    else:
         y = y + res.float()
-    if relu and relu_cols > 0:
-        y = torch.cat([y[..., :relu_cols].clamp_min(0), y[..., relu_cols:]], dim=-1)
-    elif relu:
-        y = y.clamp_min(0)
-    if emask is not None and not (accumulate and out is not None):
-        y = y * (emask.float() > 0)
+    if acc_out:
+        y = y + out.float()
+    if res is not None:
+        y = act(y)
+    if emask is not None:
+        y = torch.where(emask.float() > 0, y, torch.zeros_like(y))
     if epilogue == "pool":
         y = y.to(dtype).float()  # pool on stored-precision values, like the fused GPU epilogue
         pv, pc = maxpool_switch_ref(y)
@@ -380,10 +400,6 @@ def _conv2d_ref(x, cw, N, H, W, C, OH, OW, OC, stride, pad, relu, relu_in, in_mo
         return pv, pc.contiguous()
     odt = torch.float32 if epilogue == "f32" else dtype
     if out is not None:
-        if accumulate:  # accumulate, then mask: the kernels' order (conv2d docstring)
-            y = y + out.float()
-            if emask is not None:
-                y = y * (emask.float() > 0)
         out.copy_(y.to(out.dtype))
         return out
     return y.to(odt).contiguous()

@@ -1,16 +1,23 @@
 """Helpers shared by the exact-oracle GPU tests (test_conv_exact_gpu.py, test_conv_routes_exact_gpu.py,
-test_dream_exact_gpu.py, test_engine_exact_gpu.py through engine_oracle.py): seeded
-integer operands, the method's conditions on a CPU reference, and bit equality with it. A plain module,
+test_dream_exact_gpu.py, test_conv_rounding_exact_gpu.py, test_engine_exact_gpu.py through engine_oracle.py): seeded
+integer (and, for the rounding cases, fractional / lifted) operands, the method's conditions on a CPU reference,
+the sentinel-framed launcher and bit equality with the reference. A plain module,
 not a conftest: nothing here changes how the suite is collected or run."""
+import contextlib
+
 import pytest
 import torch
 import torch.nn.functional as F
 
+import rounding_oracle as RO
 from deconv_api_amd import ops
+from deconv_api_amd.ops import conv as Cm
 from deconv_api_amd.ops.conv import ConvWeights
+from gpu_helpers import route as _route
 
 DEV = "cuda"
 BF, HF = torch.bfloat16, torch.float16
+SENT = 7.0  # fill of the frame around an output view
 
 
 def _gen(seed):
@@ -130,3 +137,184 @@ def _recip_exact(m, cnt):
     assert torch.equal(q.double(), m.double() / cnt.double()), "sum * (1.f / count) is not the exact average"
     assert torch.equal(q, q.round()), "average is not an integer"
     return q
+
+
+# ----------------------------------------------------------------------------------------
+# launcher: a conv case on the GPU through sentinel-framed views
+# ----------------------------------------------------------------------------------------
+
+@contextlib.contextmanager
+def _policy(impl):
+    old = Cm.get_policy()
+    Cm.set_policy(impl=impl)
+    try:
+        yield
+    finally:
+        Cm.set_policy(**old)
+
+
+def _wide(t, dt, extra, fill=3.0):
+    """``t`` on the device as a channel slice of a buffer ``extra`` channels wider (row stride C + extra)."""
+    if not extra:
+        return _dev(t, dt)
+    buf = torch.full(tuple(t.shape[:-1]) + (t.shape[-1] + extra,), fill, dtype=dt, device=DEV)
+    buf[..., : t.shape[-1]] = _dev(t, dt)
+    return buf[..., : t.shape[-1]]
+
+
+def _out_view(shape, odt, left, right):
+    """A sentinel-filled buffer one image longer and ``left + right`` channels wider than ``shape`` and the view
+    of it a conv writes through."""
+    N, OC = shape[0], shape[-1]
+    buf = torch.full((N + 1,) + tuple(shape[1:-1]) + (left + OC + right,), SENT, dtype=odt, device=DEV)
+    return buf, buf[:N, ..., left: left + OC]
+
+
+def _untouched(buf, shape, left):
+    chk = buf.clone()
+    chk[: shape[0], ..., left: left + shape[-1]] = SENT
+    return bool((chk == SENT).all())
+
+
+def _launch(c, policy="auto", x_extra=0, left=0, right=8, mask_extra=0, x_fill=3.0, x_tail=False, more_extra=0,
+            **extra_kw):
+    """Run case ``c`` on the GPU under ``policy``: x (and its mask) as channel slices of buffers ``x_extra`` /
+    ``mask_extra`` wider (x's extra channels hold ``x_fill``), the output through a sentinel-framed view.
+    ``x_tail``: x is the last rows of a longer dense buffer, so it ends where the storage ends. ``more_extra``: res
+    / emask as channel slices of buffers that much wider (their row stride decides the epilogue with the output's).
+    Returns (result, route, bits_flags)."""
+    dt = c.dt
+    kw = dict(c.kw)
+    if "code" in kw:
+        kw["code"] = kw["code"].to(DEV)
+    if "mask" in kw:
+        kw["mask"] = _wide(kw["mask"], dt, mask_extra, fill=1.0)
+    for key, v in c.more.items():
+        kw[key] = _wide(v, dt, more_extra, fill=1.0)
+    oshape = tuple((c.ref[0] if c.epi == "pool" else c.ref).shape)
+    buf, view = _out_view(oshape, c.odt, left, right)
+    if c.base is not None:
+        view.copy_(_dev(c.base, c.odt))
+        kw["accumulate"] = True
+    if x_tail:
+        xbuf = torch.full((c.x.shape[0] + 3,) + tuple(c.x.shape[1:]), 3.0, dtype=dt, device=DEV)
+        xbuf[3:] = _dev(c.x, dt)
+        xd = xbuf[3:]
+    else:
+        xd = _wide(c.x, dt, x_extra, fill=x_fill)
+    with _policy(policy):
+        got = ops.conv2d(xd, c.cw.to_device(DEV, dt), out=view, **kw, **extra_kw)
+        r, bits = _route(), Cm.bits_flags()
+    assert _untouched(buf, oshape, left), "wrote outside the output view"
+    return got, r, bits
+
+
+def _expect(c, got):
+    if c.epi == "pool":
+        _same(got[0], c.ref[0])
+        assert torch.equal(got[1].cpu(), c.ref[1]), "switch codes differ"
+    else:
+        _same(got, c.ref)
+
+
+PW_H = 61  # image height of the persistent 1x1 kernel's cases (one image of PW_H x W pixels)
+
+
+def _pw_m(G, OC):
+    """Rows for about 2.25 tiles per CU with an M tail: tiles_total strictly between 2 G and 4 G, so with two
+    workgroups per CU some walk two tiles and others one."""
+    BM, BN = (128, 128) if OC % 128 == 0 else (256, 64)
+    tiles_n = -(-OC // BN)
+    tiles_m = 9 * G // (4 * tiles_n) + 1
+    W = ((tiles_m - 1) * BM + BM // 2) // PW_H  # PW_H rows of W pixels: the last row tile is about half full
+    M = PW_H * W
+    assert 2 * G < -(-M // BM) * tiles_n < 4 * G and M % BM != 0
+    return M, BM, BN
+
+
+# ----------------------------------------------------------------------------------------
+# rounding cases (test_conv_rounding_exact_gpu.py): operands whose results are INEXACT in 16 bits yet exact in
+# fp32 under any summation order, and the conditions that make bit equality with rounding_oracle.py a test of
+# where a kernel rounds
+# ----------------------------------------------------------------------------------------
+
+FRAC_Q = {BF: (5, 4), HF: (8, 7)}          # dtype -> (q, q'): bias fractions are k 2^-q, res / base are k 2^-q'
+LIFT = {BF: (256, 1024), HF: (4096, 16384)}  # the binades (spacing 2-8) the lifted biases sit in
+DENSE_INT = {BF: (15, 7), HF: (63, 31)}    # |x|, |w| limits of the bias-free cases: sums pass 2^8 / 2^11
+
+
+def _frac_bias(g, oc, dt):
+    """fp32 bias: an integer in [-4, 4] plus a multiple of 2^-q."""
+    q = FRAC_Q[dt][0]
+    return _ints(g, (oc,), -4, 4) + _ints(g, (oc,), 0, 2 ** q - 1) * 2.0 ** -q
+
+
+def _frac16(g, shape, dt):
+    """A residual / accumulate base: multiples of 2^-q' of magnitude < 16, each a ``dt`` value."""
+    qp = FRAC_Q[dt][1]
+    lim = 2 ** (qp + 4) - 1
+    v = _ints(g, shape, -lim, lim) * 2.0 ** -qp
+    assert torch.equal(v.to(dt).float(), v)
+    return v
+
+
+def _lift_bias(g, oc, dt):
+    """Three channels in four get an integer bias inside ``LIFT[dt]`` (distinct fp32 window values then often
+    round to one stored value); the fourth keeps [-4, 4], so ReLU zeros and true ties remain."""
+    lo, hi = LIFT[dt]
+    b = _ints(g, (oc,), -4, 4)
+    lifted = _ints(g, (oc,), lo, hi - 1)
+    keep = torch.arange(oc) % 4 == 3
+    return torch.where(keep, b, lifted)
+
+
+def _check_fp32_exact(y, x, cw, gbits, stride=1, pad=1, others=()):
+    """fp32-exactness: (max sum |x| |w| + max |bias| + max |res| + max |base|) 2^g < 2^24 with 2^-g the case's
+    finest granularity (every partial sum of every order is then an fp32 value), and the float64 result ``y``
+    survives fp32."""
+    bound = _absconv_max(x, cw, stride, pad) + sum(float(t.abs().max()) for t in others if t is not None)
+    assert bound * 2.0 ** gbits < 2 ** 24, "partial sums not exact in fp32"
+    fin = torch.isfinite(y)
+    assert torch.equal(y[fin].float().double(), y[fin]), "result not exact in fp32"
+    for t in (y,) + tuple(t for t in others if t is not None):
+        s = t.double() * 2.0 ** gbits
+        assert torch.equal(s, s.round()), "operand finer than the stated granularity"
+
+
+def _check_rounding(y, dt):
+    """Rounding density of the float64 result ``y`` for output type ``dt``: >= 20 % not representable, >= 5 %
+    exact ties, ties resolved downward and upward each >= 2 %; and _check_exact's density conditions."""
+    inexact = ~RO.representable(y, dt)
+    r = RO.round16(y, dt)
+    assert torch.equal(inexact, r != y), "representability test disagrees with the conversion"
+    tie = RO.ties(y, dt)
+    n = y.numel()
+    f = lambda m: float(m.sum()) / n
+    assert f(inexact) >= 0.20, f"only {f(inexact):.3f} of the outputs are inexact in {dt}"
+    assert f(tie) >= 0.05, f"only {f(tie):.3f} of the outputs are exact ties"
+    assert f(tie & (r < y)) >= 0.02 and f(tie & (r > y)) >= 0.02, \
+        f"ties resolve down / up in {f(tie & (r < y)):.3f} / {f(tie & (r > y)):.3f} of the outputs"
+    assert f(y != 0) >= 0.25, "too few non-zero outputs"
+    assert r.flatten()[:65536].unique().numel() >= 16, "too few distinct values"
+
+
+def _check_separation(one, two, OC):
+    """Model separation: the once- and twice-rounded oracles differ on >= 5 % of the outputs, and inside the last
+    partial 8-channel chunk where OC % 8 != 0."""
+    d = one != two
+    assert float(d.float().mean()) >= 0.05, f"models differ on {float(d.float().mean()):.3f} of the outputs only"
+    if OC % 8:
+        assert bool(d[..., OC - OC % 8:].any()), "models agree on the last partial chunk"
+
+
+def _check_pool_separation(full, dt):
+    """Pool separation on the unrounded ReLU'd map ``full`` (float64): first-max codes of the ROUNDED map differ
+    from those of the unrounded one in >= 1 % of the windows; the rounded map is tie-rich (_check_ties).
+    Returns (pooled values, codes) of the rounded map: round, then pool."""
+    rv, rc = RO.pool_first_max(RO.round16(full, dt))
+    ev, ec = RO.pool_first_max(full)
+    assert torch.equal(RO.round16(ev, dt), rv), "pooled values depend on the rounding point"
+    sep = float((rc != ec).float().mean())
+    assert sep >= 0.01, f"codes differ in {sep:.4f} of the windows only"
+    _check_ties(RO.round16(full, dt))
+    return rv, rc

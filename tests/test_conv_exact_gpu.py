@@ -380,6 +380,33 @@ def test_exact_accumulate_then_emask(native_lib, name, shape, tune, route, dt):
 
 
 @pytest.mark.parametrize("dt", [BF, HF])
+def test_exact_res_accumulate_relu_order(native_lib, dt):
+    """res + accumulate + ReLU (+ emask) on integer operands: the documented order is += res, += out, THEN the
+    ReLU, then the mask. The CPU path follows it (a negative base under a positive conv + res tells
+    relu(conv + res) + out from relu(conv + res + out)); the GPU binding takes res only without accumulate and
+    must refuse the combination, not run it in some other order."""
+    N, H, W, C, OC = 2, 9, 7, 64, 128
+    g = _gen(41)
+    x = _ints(g, (N, H, W, C), -3, 3)
+    cw = _weights(g, OC, C)
+    res, em = _ints(g, (N, H, W, OC), -4, 4), _signs(g, (N, H, W, OC))
+    base = _ints(g, (N, H, W, OC), 1, 4) * torch.where(torch.rand(N, H, W, OC, generator=g) < 0.5, -1.0, 1.0)
+    conv = ops.conv2d(x, cw, relu=False)
+    _check_exact(conv, dt, x, cw, 12.0)
+    want = (conv + res + base).clamp_min(0)
+    other = (conv + res).clamp_min(0) + base
+    _check_exact(want, dt, x, cw, 12.0)
+    assert float((want != other).float().mean()) > 0.10, "the two orders do not differ on this case"
+    want = want * (em > 0)
+    for t in (torch.float32, dt):
+        ref = ops.conv2d(x.to(t), cw, relu=True, res=res.to(t), emask=em.to(t), out=base.to(t).clone(), accumulate=True)
+        _same(ref, want)
+    with pytest.raises(RuntimeError, match="res: forward conv"):
+        ops.conv2d(_dev(x, dt), cw.to_device(DEV, dt), relu=True, res=_dev(res, dt), emask=_dev(em, dt),
+                   out=_dev(base, dt), accumulate=True)
+
+
+@pytest.mark.parametrize("dt", [BF, HF])
 @pytest.mark.parametrize("C,OC,stride", [(64, 128, 1), (32, 64, 2), (128, 256, 1)])
 def test_exact_a_mask_zeros(native_lib, dt, C, OC, stride):
     """The A-operand ReLU mask (dgrad through a ReLU) drawn from {-1, -0.0, 0, 1}, forward and stride-2

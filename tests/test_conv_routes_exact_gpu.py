@@ -24,7 +24,6 @@ automatic split-K on).
 Cases whose grid must exceed the CU count take the count as a parameter: ``gpu_helpers.cus()`` on the GPU,
 ``G_NOMINAL`` in ``test_conditions``.
 """
-import contextlib
 import functools
 import types
 
@@ -34,12 +33,11 @@ import torch
 
 from deconv_api_amd import ops
 from deconv_api_amd.ops import conv as Cm
-from exact_helpers import (BF, DEV, HF, _check_exact, _check_ties, _dev, _gen, _geom, _ints, _pool_case, _same, _signs,
-                           _weights)
+from exact_helpers import (BF, DEV, HF, SENT, _check_exact, _check_ties, _dev, _expect, _gen, _geom, _ints, _launch,
+                           _out_view, _policy, _pool_case, _pw_m, PW_H, _same, _signs, _untouched, _weights)
 from gpu_helpers import cus as _cus, route as _route, tune as _tune
 
 gpu = pytest.mark.gpu
-SENT = 7.0
 G_NOMINAL = 256  # the CU count test_conditions builds the CU-following cases for
 F32 = torch.float32
 
@@ -103,78 +101,6 @@ def _case(seed, N, H, W, C, OC, k=(3, 3), stride=1, pad=None, dt=BF, epi="bf16",
         ref = plain
     return types.SimpleNamespace(x=x, cw=cw, kw=kw, more=more, base=base, ref=ref, dt=dt, odt=odt, OC=OC, C=C, N=N,
                                  epi=epi)
-
-
-@contextlib.contextmanager
-def _policy(impl):
-    old = Cm.get_policy()
-    Cm.set_policy(impl=impl)
-    try:
-        yield
-    finally:
-        Cm.set_policy(**old)
-
-
-def _wide(t, dt, extra, fill=3.0):
-    """``t`` on the device as a channel slice of a buffer ``extra`` channels wider (row stride C + extra)."""
-    if not extra:
-        return _dev(t, dt)
-    buf = torch.full(tuple(t.shape[:-1]) + (t.shape[-1] + extra,), fill, dtype=dt, device=DEV)
-    buf[..., : t.shape[-1]] = _dev(t, dt)
-    return buf[..., : t.shape[-1]]
-
-
-def _out_view(shape, odt, left, right):
-    """A sentinel-filled buffer one image longer and ``left + right`` channels wider than ``shape`` and the view
-    of it a conv writes through."""
-    N, OC = shape[0], shape[-1]
-    buf = torch.full((N + 1,) + tuple(shape[1:-1]) + (left + OC + right,), SENT, dtype=odt, device=DEV)
-    return buf, buf[:N, ..., left: left + OC]
-
-
-def _untouched(buf, shape, left):
-    chk = buf.clone()
-    chk[: shape[0], ..., left: left + shape[-1]] = SENT
-    return bool((chk == SENT).all())
-
-
-def _launch(c, policy="auto", x_extra=0, left=0, right=8, mask_extra=0, x_fill=3.0, x_tail=False, **extra_kw):
-    """Run case ``c`` on the GPU under ``policy``: x (and its mask) as channel slices of buffers ``x_extra`` /
-    ``mask_extra`` wider (x's extra channels hold ``x_fill``), the output through a sentinel-framed view.
-    ``x_tail``: x is the last rows of a longer dense buffer, so it ends where the storage ends.
-    Returns (result, route, bits_flags)."""
-    dt = c.dt
-    kw = dict(c.kw)
-    if "code" in kw:
-        kw["code"] = kw["code"].to(DEV)
-    if "mask" in kw:
-        kw["mask"] = _wide(kw["mask"], dt, mask_extra, fill=1.0)
-    for key, v in c.more.items():
-        kw[key] = _dev(v, dt)
-    oshape = tuple((c.ref[0] if c.epi == "pool" else c.ref).shape)
-    buf, view = _out_view(oshape, c.odt, left, right)
-    if c.base is not None:
-        view.copy_(_dev(c.base, c.odt))
-        kw["accumulate"] = True
-    if x_tail:
-        xbuf = torch.full((c.x.shape[0] + 3,) + tuple(c.x.shape[1:]), 3.0, dtype=dt, device=DEV)
-        xbuf[3:] = _dev(c.x, dt)
-        xd = xbuf[3:]
-    else:
-        xd = _wide(c.x, dt, x_extra, fill=x_fill)
-    with _policy(policy):
-        got = ops.conv2d(xd, c.cw.to_device(DEV, dt), out=view, **kw, **extra_kw)
-        r, bits = _route(), Cm.bits_flags()
-    assert _untouched(buf, oshape, left), "wrote outside the output view"
-    return got, r, bits
-
-
-def _expect(c, got):
-    if c.epi == "pool":
-        _same(got[0], c.ref[0])
-        assert torch.equal(got[1].cpu(), c.ref[1]), "switch codes differ"
-    else:
-        _same(got, c.ref)
 
 
 def _bits_of(t):
@@ -590,21 +516,6 @@ def test_halo_stream_bits(native_lib, monkeypatch, N, H, W, C, OC, dt, route):
 # ----------------------------------------------------------------------------------------
 # 4. persistent 1x1 (csrc/conv_pw.hip)
 # ----------------------------------------------------------------------------------------
-
-PW_H = 61  # image height of the 1x1 cases (one image of PW_H x W pixels)
-
-
-def _pw_m(G, OC):
-    """Rows for about 2.25 tiles per CU with an M tail: tiles_total strictly between 2 G and 4 G, so with two
-    workgroups per CU some walk two tiles and others one."""
-    BM, BN = (128, 128) if OC % 128 == 0 else (256, 64)
-    tiles_n = -(-OC // BN)
-    tiles_m = 9 * G // (4 * tiles_n) + 1
-    W = ((tiles_m - 1) * BM + BM // 2) // PW_H  # PW_H rows of W pixels: the last row tile is about half full
-    M = PW_H * W
-    assert 2 * G < -(-M // BM) * tiles_n < 4 * G and M % BM != 0
-    return M, BM, BN
-
 
 PW = {
     # name -> (C, OC, dtype, case options, x_extra)
