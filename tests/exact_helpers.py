@@ -1,6 +1,7 @@
 """Helpers shared by the exact-oracle GPU tests (test_conv_exact_gpu.py, test_conv_routes_exact_gpu.py,
-test_dream_exact_gpu.py, test_conv_rounding_exact_gpu.py, test_engine_exact_gpu.py through engine_oracle.py): seeded
-integer (and, for the rounding cases, fractional / lifted) operands, the method's conditions on a CPU reference,
+test_dream_exact_gpu.py, test_conv_rounding_exact_gpu.py, test_small_values_exact_gpu.py, test_engine_exact_gpu.py
+through engine_oracle.py): seeded integer (and, for the rounding cases, fractional / lifted) operands, mask draws
+(``_signs``; ``_signs_tiny`` for the predicate on tiny values), the method's conditions on a CPU reference,
 the sentinel-framed launcher and bit equality with the reference. A plain module,
 not a conftest: nothing here changes how the suite is collected or run."""
 import contextlib
@@ -44,6 +45,23 @@ def _signs(g, shape):
     """Mask values from {-1, -0.0, 0, 1}: the two zeros must mask like the negatives."""
     vals = torch.tensor([-1.0, -0.0, 0.0, 1.0])
     return vals[torch.randint(0, 4, shape, generator=g)]
+
+
+TINY_BITS = {BF: (0x0001, 0x0080), HF: (0x0001, 0x0400)}  # dtype -> bits of the smallest subnormal / normal
+
+
+def _signs_tiny(g, shape, dt):
+    """Stored mask values +-1, +-0.0, +-(smallest subnormal, bits 0x0001 / 0x8001) and +-(smallest normal) of
+    ``dt``, equally often, as a ``dt`` tensor (fp32 would hold them too, but the bits are the point). Positive as
+    real numbers: 1 and the two positive tiny values; the six others must mask."""
+    sub, nrm = TINY_BITS[dt]
+    one = int(torch.ones((), dtype=dt).view(torch.int16))
+    bits = torch.tensor([one, 0x0000, sub, nrm], dtype=torch.int32)
+    bits = torch.cat([bits, bits | 0x8000])
+    bits = torch.where(bits >= 0x8000, bits - 0x10000, bits).to(torch.int16)
+    vals = bits.view(dt)
+    assert int((vals.double() > 0).sum()) == 3 and bool(torch.isfinite(vals.float()).all())
+    return vals[torch.randint(0, 8, shape, generator=g)]
 
 
 def _absconv_max(x, cw, stride=1, pad=1):
@@ -177,27 +195,29 @@ def _untouched(buf, shape, left):
 
 
 def _launch(c, policy="auto", x_extra=0, left=0, right=8, mask_extra=0, x_fill=3.0, x_tail=False, more_extra=0,
-            **extra_kw):
+            mask_fill=1.0, more_fill=1.0, **extra_kw):
     """Run case ``c`` on the GPU under ``policy``: x (and its mask) as channel slices of buffers ``x_extra`` /
     ``mask_extra`` wider (x's extra channels hold ``x_fill``), the output through a sentinel-framed view.
-    ``x_tail``: x is the last rows of a longer dense buffer, so it ends where the storage ends. ``more_extra``: res
-    / emask as channel slices of buffers that much wider (their row stride decides the epilogue with the output's).
+    ``x_tail``: x is the last rows of a longer dense buffer, so it ends where the storage ends (its leading rows
+    hold ``x_fill``). ``more_extra``: res / emask as channel slices of buffers that much wider (their row stride
+    decides the epilogue with the output's). ``mask_fill`` / ``more_fill``: what the mask's and res / emask's extra
+    channels hold.
     Returns (result, route, bits_flags)."""
     dt = c.dt
     kw = dict(c.kw)
     if "code" in kw:
         kw["code"] = kw["code"].to(DEV)
     if "mask" in kw:
-        kw["mask"] = _wide(kw["mask"], dt, mask_extra, fill=1.0)
+        kw["mask"] = _wide(kw["mask"], dt, mask_extra, fill=mask_fill)
     for key, v in c.more.items():
-        kw[key] = _wide(v, dt, more_extra, fill=1.0)
+        kw[key] = _wide(v, dt, more_extra, fill=more_fill)
     oshape = tuple((c.ref[0] if c.epi == "pool" else c.ref).shape)
     buf, view = _out_view(oshape, c.odt, left, right)
     if c.base is not None:
         view.copy_(_dev(c.base, c.odt))
         kw["accumulate"] = True
     if x_tail:
-        xbuf = torch.full((c.x.shape[0] + 3,) + tuple(c.x.shape[1:]), 3.0, dtype=dt, device=DEV)
+        xbuf = torch.full((c.x.shape[0] + 3,) + tuple(c.x.shape[1:]), x_fill, dtype=dt, device=DEV)
         xbuf[3:] = _dev(c.x, dt)
         xd = xbuf[3:]
     else:

@@ -97,19 +97,30 @@ def staged(acc, bias, relu, dt, res=None, base=None, emask=None, relu_cols=0):
     return _mask(round16(t, dt), emask)
 
 
-def representable(v, dt):
-    """Elementwise: float64 ``v`` is a ``dt`` value (normal range)."""
-    m, _ = torch.frexp(v)
-    s = m * float(2 ** SIG[dt])
+MIN_NORMAL_EXP = {torch.bfloat16: -126, torch.float16: -14}  # smallest normal 2^e; below it the grid is fixed
+SUB_GRID_EXP = {dt: e - (SIG[dt] - 1) for dt, e in MIN_NORMAL_EXP.items()}  # 2^-133 (bf16), 2^-24 (fp16)
+
+
+def _on_grid(v, dt, extra):
+    """``v`` is a multiple of its ``dt`` spacing / 2^extra: the binade's spacing in the normal range (frexp: |v| =
+    m 2^e with m in [0.5, 1), spacing 2^(e - SIG)), the fixed grid 2^SUB_GRID_EXP below the smallest normal."""
+    m, e = torch.frexp(v)
+    s = m * float(2 ** (SIG[dt] + extra))
+    # below 2^MIN_NORMAL_EXP: e <= MIN_NORMAL_EXP, and the spacing stays 2^(MIN_NORMAL_EXP + 1 - SIG)
+    shift = (MIN_NORMAL_EXP[dt] + 1 - e).clamp_min(0)
+    s = torch.ldexp(s, -shift)
     return s == s.round()
+
+
+def representable(v, dt):
+    """Elementwise: float64 ``v`` is a finite ``dt`` value, normal or subnormal (0 included)."""
+    return _on_grid(v, dt, 0)
 
 
 def ties(v, dt):
     """Elementwise: ``v`` lies exactly half way between two neighbouring ``dt`` values (one more significand bit
-    holds it, ``dt`` does not)."""
-    m, _ = torch.frexp(v)
-    s = m * float(2 ** (SIG[dt] + 1))
-    return (s == s.round()) & ~representable(v, dt)
+    holds it, ``dt`` does not; below the smallest normal: an odd multiple of half the fixed grid)."""
+    return _on_grid(v, dt, 1) & ~representable(v, dt)
 
 
 def windows(full):
